@@ -29,6 +29,10 @@ and four bins per rank against a direct fp64 DFT sum; the entry reports the thre
 exchange, row passes: HIP events on the one stream), the communicator's size, the RCCL version and whether the fallback transport
 was taken, and under N > 1 the line carries every rank's kernel time.
 
+`--dump-outputs DIR` writes, after the timed steps, what the last of them computed: rank 0's spectra as float32 DIR/out_re.npy and
+DIR/out_im.npy, one row per transform, for a fixed seeded sample of at most DUMP_TRANSFORMS transforms of the batch (their indices in
+DIR/transform_index.npy). The input is a pure function of the arguments, so two builds can be compared output for output.
+
 Failure policy: a failed self-check of the HEADLINE ends the run without a line (a broken kernel cannot post a number). Every
 `other_configs` entry, configs[4b] included, is isolated: a failed check or an exception becomes {"error": ...} under the entry's
 name, the line is still printed, and the process exits with code 1 (3 when the configs[4b] entry had to be abandoned after
@@ -53,6 +57,8 @@ MFMA_PEAK_TFLOPS = 2500.0      # dense fp16 MFMA
 REL_L2_TOL = 1.5e-3            # the library's stated tolerance against the fp64 DFT/N (tests/test_gpu_parity.py)
 
 RAMP = 100          # untimed launches before the warmup steps (GPU clock ramp, ~35 ms); the cold figure is reported too
+DUMP_TRANSFORMS = 1024   # --dump-outputs: at most this many transforms of the batch (2 x 1024 x 4096 float32 = 32 MiB)
+DUMP_SEED = 20260        # --dump-outputs: fixed choice of the sampled transforms
 
 
 def usable_cores(omp_threads):
@@ -172,6 +178,26 @@ def check_transforms(torch, orc, y, n, batch, ids, first_fft=0, seed=SEED, perm=
     if not worst < REL_L2_TOL:
         raise CheckFailed(f"self-check failed: N={n} rel-L2 error {worst:.3e} vs the CPU oracle")
     return worst
+
+
+def dump_outputs(torch, y, n, batch, out_dir):
+    """--dump-outputs: the spectra the last timed step left in y ([fft_i RE | fft_i IM] blocks of n fp16 each), widened to float32
+    (exact) and written as out_dir/out_re.npy and out_im.npy, shape (transforms, n). A batch of more than DUMP_TRANSFORMS transforms
+    is sampled by a fixed seeded choice of transform indices, the same in every run with the same --batch; out_dir/transform_index.npy
+    (float64) names them. Returns the description that goes into the result line."""
+    import numpy as np
+
+    if batch <= DUMP_TRANSFORMS:
+        ids = np.arange(batch)
+    else:
+        ids = np.sort(np.random.default_rng(DUMP_SEED).choice(batch, DUMP_TRANSFORMS, replace=False))
+    blocks = y.view(batch, 2, n).index_select(0, torch.from_numpy(ids).to(y.device)).float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    files = {"out_re": blocks[:, 0], "out_im": blocks[:, 1], "transform_index": ids.astype(np.float64)}
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
+    return {"dir": out_dir, "files": {k + ".npy": list(v.shape) for k, v in files.items()}, "transforms": int(len(ids)),
+            "of_batch": batch, "sample_seed": DUMP_SEED if batch > DUMP_TRANSFORMS else None}
 
 
 def other_configs(torch, tf, orc, device):
@@ -639,7 +665,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short extra measurements of the other BASELINE configs (reported under 'other_configs')")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (rank 0's output; a fixed seeded sample of at most "
+                         f"{DUMP_TRANSFORMS} transforms) as float32 DIR/out_re.npy and DIR/out_im.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch                     # (importing torch and counting devices do not initialise the GPU)
 
@@ -648,14 +679,18 @@ def main():
         # only load the prebuilt library.
         import __graft_entry__ as g
 
-        g.build()
+        if not g.is_current():
+            g.build()
         sys.exit(self_launch(args.gpus, os.path.abspath(__file__), sys.argv[1:], nproc_visible=torch.cuda.device_count()))
 
     import __graft_entry__ as g
 
-    # recompiled here, or the prebuilt library that travelled with the tree (build() is mtime-based)?
-    build_mode = "reused: prebuilt libtfft.so newer than its sources" if g.is_current() else "recompiled by this run"
-    g.build()
+    # recompiled here, or the prebuilt library that travelled with the tree (build() is mtime-based)? build() runs only when the
+    # library is stale: the benchmark may run from a tree built beforehand that it cannot write to
+    prebuilt = g.is_current()
+    build_mode = "reused: prebuilt libtfft.so newer than its sources" if prebuilt else "recompiled by this run"
+    if not prebuilt:
+        g.build()
     import tensor_fft_amd as tf
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -731,6 +766,8 @@ def main():
         t = torch.tensor([wall, kernel_ms, cold_ms], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall, kernel_ms, cold_ms = float(t[0]), float(t[1]), float(t[2])
+    # what the last timed step computed, before anything else runs on y
+    dumped = dump_outputs(torch, y, N, batch, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # per-launch spread (SURVEY 8d asks for mean and sigma; the true mean, not the reference's sum / (n - 1),
     # BenchUtil.h:41-48): 20 individually timed launches after the timed region, not part of `value`
@@ -838,6 +875,8 @@ def main():
             "build_mode": build_mode,
             "library": tf.lib_path() if hasattr(tf, "lib_path") else None,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if world == 1 and not args.no_other_configs and not args.only_dist_entry and batch == BATCH:
             x = y = None
             torch.cuda.empty_cache()

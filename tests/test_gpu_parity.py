@@ -74,7 +74,7 @@ def _check_against_oracle(orc, re, im, got_re, got_im, mode):
 
 def test_instruction_semantics_probe():
     exe = os.path.join(ROOT, "tools", "probe_gfx950")
-    if not os.path.exists(exe):
+    if not os.path.exists(exe) or os.path.getmtime(exe) < os.path.getmtime(exe + ".hip"):
         subprocess.check_call(["hipcc", "-O2", "--offload-arch=gfx950", "-o", exe, exe + ".hip"])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     print(r.stdout)
