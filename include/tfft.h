@@ -306,6 +306,57 @@ int tfft_exec(const tfft_plan* plan, const void* in_re, const void* in_im, void*
 int tfft_exec_inverse(const tfft_plan* plan, const void* in_re, const void* in_im, void* out_re,
                       void* out_im, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Real-input transforms (R2C / C2R) of `batch` real fp16 signals of length n (16 <= n <= 2^30, a power of two).
+ *
+ * Layout. Real signal s lives at in + s * real_stride halves (tfft_plan_opts.in_batch_stride, 0 = n). Its half spectrum, bins
+ * 0 .. n/2, lives at out_re + s * spectrum_stride and out_im + s * spectrum_stride (tfft_plan_opts.out_batch_stride, 0 = 2 h with
+ * h = tfft_rplan_spectrum_pitch(n) = round_up(n/2 + 1, 8): the block [RE h | IM h] per signal, both planes 16-byte aligned; for
+ * n = 4096, h = 2056). Any multiple of 8 >= n/2 + 1 is accepted as spectrum stride, any multiple of 8 >= n as real stride. The
+ * halves beyond bin n/2 are never written. C2R reads the spectrum and writes the real signals with the same two strides.
+ *
+ * Conventions (those of the complex plans, tfft_plan_opts.scale honoured the same way):
+ *   R2C  bins 0 .. n/2 of DFT(x)/n under the default sequential scaling, i.e. numpy.fft.rfft(x) / n.
+ *   C2R  what tfft_exec_inverse returns for the Hermitian extension of the half spectrum, IM dropped; the IM of bins 0 and n/2 is
+ *        ignored (as numpy and cuFFT do). With the default scaling this is numpy.fft.irfft(X, n), so C2R(R2C(x)) = x / n.
+ * R2C never writes its input and C2R never writes its input spectrum (the merged spectrum goes to the workspace); in-place
+ * execution, and outputs that overlap anything else, are refused (TFFT_ERR_ARG). Pointers: 16-byte aligned.
+ *
+ * Method: signals 2p and 2p + 1 are the RE and IM planes of one complex transform, Z = DFT(a + i b) / n, read without a copy,
+ * and the two half spectra follow from Z[k] and Z[n-k] (csrc/rsplit.hpp: fp32 add, exact * 0.5, one rounding to fp16). An odd
+ * batch pairs its last signal with itself. n = 4096: R2C is ONE pass over HBM (the N = 4096 kernel with the split fused into its
+ * epilogue, about 4 bytes per real sample); other n: the complex plan into the workspace, then a split pass. C2R: a merge pass into
+ * the workspace, then the inverse complex plan straight into the real buffer.
+ *
+ * Accuracy. Pairing mixes the two signals' errors: the error of a bin of either half spectrum is bounded relative to the largest
+ * bin of the PAIR's complex spectrum Z (the same kind of bound the complex path states per transform), not relative to the signal's
+ * own spectrum. A quiet signal paired with a loud one inherits an error of the order of 1e-3 x the loud one's largest bin. Pair
+ * signals of similar magnitude, or give quiet signals batches of their own, where that matters.
+ *
+ * opts: NULL or a tfft_plan_opts; only in_batch_stride, out_batch_stride, scale and launch_iters may be non-zero (inner > 1,
+ * transposed orders, fourstep_*, preserve_input and every variant bit are refused). At n = 4096 the forward transform is always
+ * the N = 4096 kernel (plan wisdom loaded with tfft_tuning_load / _add does not apply to it); other sub-plans follow the complex
+ * plans' defaults, wisdom included. The workspace (tfft_rplan_workspace_bytes) is sized at creation
+ * for both directions; hand it in (256-byte aligned, at least that size) or call tfft_rplan_prepare once, otherwise the first
+ * execution allocates it. After either, executions only launch kernels (no allocation; stream capture works). Executions of one
+ * plan must not overlap in time. */
+typedef struct tfft_rplan tfft_rplan;
+enum { TFFT_RPLAN_TWO_PASS = 1 };   /* flags: the generic split path at every n (n = 4096 too), for A/B and tests */
+int tfft_rplan_create(uint64_t n, uint64_t batch, int device_id, const tfft_plan_opts* opts, int flags, tfft_rplan** out);
+void tfft_rplan_destroy(tfft_rplan* plan);
+/* Host only: h above (0 for an unsupported n). */
+uint64_t tfft_rplan_spectrum_pitch(uint64_t n);
+/* Host only: the kernels of both directions as text, "r2c: k4096:4096+split | c2r: merge k4096:4096" (fused) or
+ * "r2c: <complex chain> split | c2r: merge <complex chain>"; refuses what tfft_rplan_create refuses on the same n, batch, flags. */
+int tfft_rplan_describe(uint64_t n, uint64_t batch, int flags, char* buf, size_t bytes);
+/* Kernel launches of one R2C (c2r = 0) or C2R (c2r = 1) execution. */
+int tfft_rplan_num_launches(const tfft_rplan* plan, int c2r);
+size_t tfft_rplan_workspace_bytes(const tfft_rplan* plan);
+int tfft_rplan_set_workspace(tfft_rplan* plan, void* device_ptr, size_t bytes);
+int tfft_rplan_prepare(tfft_rplan* plan);
+int tfft_exec_r2c(const tfft_rplan* plan, const void* in, void* out_re, void* out_im, void* stream);
+int tfft_exec_c2r(const tfft_rplan* plan, const void* in_re, const void* in_im, void* out, void* stream);
+
 /* 2D transform of `batch` images [rows][cols] (BASELINE config "2D 4096 x 4096, batch 64"; the reference has no 2D
  * entry point, this is its 1D path (ComputeFFT.h:162-293) used twice): a row pass over contiguous lines (N = cols,
  * batch * rows transforms) and a column pass along the strided axis (N = rows, inner = cols). Layout: fully planar,

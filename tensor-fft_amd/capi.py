@@ -27,6 +27,8 @@ SYMBOLS = [
     "tfft_copy_h2d", "tfft_copy_d2h", "tfft_plan_prepare", "tfft_plan_opts_init", "tfft_plan_opts_known_size",
     "tfft_dist_rccl_version", "tfft_dist_comm_info", "tfft_kernel_list",
     "tfft_tuning_load", "tfft_tuning_add", "tfft_tuning_clear", "tfft_tuning_query", "tfft_abi_version",
+    "tfft_rplan_create", "tfft_rplan_destroy", "tfft_rplan_spectrum_pitch", "tfft_rplan_describe", "tfft_rplan_num_launches",
+    "tfft_rplan_workspace_bytes", "tfft_rplan_set_workspace", "tfft_rplan_prepare", "tfft_exec_r2c", "tfft_exec_c2r",
 ]
 ABI_VERSION = 2                                               # TFFT_ABI_VERSION this binding's struct mirrors were written against
 
@@ -243,6 +245,26 @@ def load_library():
     L.tfft_dist_comm_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
     L.tfft_dist_rccl_version.restype = ci
     L.tfft_dist_rccl_version.argtypes = [ctypes.POINTER(ci)]
+    L.tfft_rplan_create.restype = ci
+    L.tfft_rplan_create.argtypes = [u64, u64, ci, ctypes.POINTER(PlanOpts), ci, ctypes.POINTER(vp)]
+    L.tfft_rplan_destroy.restype = None
+    L.tfft_rplan_destroy.argtypes = [vp]
+    L.tfft_rplan_spectrum_pitch.restype = u64
+    L.tfft_rplan_spectrum_pitch.argtypes = [u64]
+    L.tfft_rplan_describe.restype = ci
+    L.tfft_rplan_describe.argtypes = [u64, u64, ci, ctypes.c_char_p, ctypes.c_size_t]
+    L.tfft_rplan_num_launches.restype = ci
+    L.tfft_rplan_num_launches.argtypes = [vp, ci]
+    L.tfft_rplan_workspace_bytes.restype = ctypes.c_size_t
+    L.tfft_rplan_workspace_bytes.argtypes = [vp]
+    L.tfft_rplan_set_workspace.restype = ci
+    L.tfft_rplan_set_workspace.argtypes = [vp, vp, ctypes.c_size_t]
+    L.tfft_rplan_prepare.restype = ci
+    L.tfft_rplan_prepare.argtypes = [vp]
+    L.tfft_exec_r2c.restype = ci
+    L.tfft_exec_r2c.argtypes = [vp, vp, vp, vp, vp]
+    L.tfft_exec_c2r.restype = ci
+    L.tfft_exec_c2r.argtypes = [vp, vp, vp, vp, vp]
     L.tfft_last_error.restype = ctypes.c_char_p
     L.tfft_last_error.argtypes = []
     L.tfft_version.restype = ctypes.c_char_p
@@ -424,6 +446,178 @@ class TfftPlan:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
             self.exec_ptr(in_re.data_ptr(), in_im.data_ptr(), out_re.data_ptr(), out_im.data_ptr(), stream)
+
+
+RPLAN_TWO_PASS = 1                                            # tfft_rplan_create flags
+
+
+def rplan_spectrum_pitch(n):
+    """tfft_rplan_spectrum_pitch: halves per plane of one half spectrum in the default layout, round_up(n/2 + 1, 8). Host only."""
+    return int(load_library().tfft_rplan_spectrum_pitch(int(n)))
+
+
+def rplan_describe(n, batch=1, two_pass=False):
+    """tfft_rplan_describe: the kernels of both directions of a real-input plan, as text. Host only, no GPU needed."""
+    buf = ctypes.create_string_buffer(512)
+    _check(load_library().tfft_rplan_describe(int(n), int(batch), RPLAN_TWO_PASS if two_pass else 0, buf, len(buf)))
+    return buf.value.decode()
+
+
+class TfftRealPlan:
+    """Owning wrapper of tfft_rplan: `batch` real fp16 signals of length n <-> their half spectra, bins 0 .. n/2 (include/tfft.h).
+
+    in_batch_stride: halves between real signals (0 = n); out_batch_stride: halves between half spectra of a plane (0 = 2 h, the
+    [RE h | IM h] block, h = rplan_spectrum_pitch(n)). r2c(x, out_re, out_im) = rfft(x) / n and c2r(in_re, in_im, out) =
+    irfft(X, n) under the default scaling; both take torch CUDA float16 tensors."""
+
+    def __init__(self, n, batch=1, device=0, in_batch_stride=0, out_batch_stride=0, scale="sequential", two_pass=False, launch_iters=0):
+        L = load_library()
+        self._lib = L
+        self._h = ctypes.c_void_p()
+        scale = _SCALES[scale] if isinstance(scale, str) else int(scale)
+        opts = PlanOpts(ctypes.sizeof(PlanOpts), 0, int(in_batch_stride), int(out_batch_stride), 0, 0, 0, scale, 0, 0, 0,
+                        int(launch_iters), 0)
+        _check(L.tfft_rplan_create(int(n), int(batch), int(device), ctypes.byref(opts), RPLAN_TWO_PASS if two_pass else 0,
+                                   ctypes.byref(self._h)))
+        self.n, self.batch, self.device, self.scale = int(n), int(batch), int(device), scale
+        self.bins = self.n // 2 + 1
+        self.pitch = rplan_spectrum_pitch(self.n)
+        self.in_batch_stride = int(in_batch_stride) or self.n
+        self.out_batch_stride = int(out_batch_stride) or 2 * self.pitch
+        self._ws = None
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._h = None
+            self._lib.tfft_rplan_destroy(h)
+
+    __del__ = close
+
+    def num_launches(self, c2r=False):
+        return int(self._lib.tfft_rplan_num_launches(self._h, int(bool(c2r))))
+
+    @property
+    def workspace_bytes(self):
+        return int(self._lib.tfft_rplan_workspace_bytes(self._h))
+
+    def set_workspace(self, tensor):
+        """Hands a torch CUDA tensor in as the plan's workspace (kept alive by the plan)."""
+        _check(self._lib.tfft_rplan_set_workspace(self._h, tensor.data_ptr(), tensor.numel() * tensor.element_size()))
+        self._ws = tensor
+
+    def prepare(self):
+        """Allocates the plan's own workspace now (tfft_rplan_prepare): later executions only launch kernels."""
+        _check(self._lib.tfft_rplan_prepare(self._h))
+
+    def _check_tensors(self, real, s_re, s_im):
+        import torch
+
+        for t in (real, s_re, s_im):
+            if not (t.is_cuda and t.dtype == torch.float16 and t.is_contiguous()):
+                raise TfftError(5, "buffers must be contiguous CUDA float16 tensors")
+            if t.device.index != self.device:
+                raise TfftError(5, "tensor on another device than the plan")
+        if real.numel() < (self.batch - 1) * self.in_batch_stride + self.n:
+            raise TfftError(5, "the real buffer is shorter than (batch-1)*in_batch_stride + n")
+        need = (self.batch - 1) * self.out_batch_stride + self.bins
+        if s_re.numel() < need or s_im.numel() < need:
+            raise TfftError(5, "a spectrum plane is shorter than (batch-1)*out_batch_stride + n/2 + 1")
+
+    def _stream(self, stream):
+        import torch
+
+        return torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+
+    def r2c_ptr(self, x, out_re, out_im, stream=0):
+        _check(self._lib.tfft_exec_r2c(self._h, x, out_re, out_im, stream))
+
+    def c2r_ptr(self, in_re, in_im, out, stream=0):
+        _check(self._lib.tfft_exec_c2r(self._h, in_re, in_im, out, stream))
+
+    def r2c(self, x, out_re, out_im, stream=None):
+        """Half spectra of the real signals in x into the planes out_re / out_im (tfft_exec_r2c)."""
+        import torch
+
+        self._check_tensors(x, out_re, out_im)
+        with torch.cuda.device(self.device):
+            self.r2c_ptr(x.data_ptr(), out_re.data_ptr(), out_im.data_ptr(), self._stream(stream))
+
+    def c2r(self, in_re, in_im, out, stream=None):
+        """Real signals of the half spectra in in_re / in_im into out (tfft_exec_c2r)."""
+        import torch
+
+        self._check_tensors(out, in_re, in_im)
+        with torch.cuda.device(self.device):
+            self.c2r_ptr(in_re.data_ptr(), in_im.data_ptr(), out.data_ptr(), self._stream(stream))
+
+
+# rfft / irfft keep the plans of the last RPLAN_CACHE_SIZE (n, batch, device) shapes, least recently used first out. A plan holds
+# device memory outside torch's allocator: its tables, and from its first C2R (or two-pass R2C) a workspace of about twice the
+# input. A caller with many shapes should hold TfftRealPlan objects itself; rplan_cache_clear() releases the cached ones.
+RPLAN_CACHE_SIZE = 8
+_rplans = {}
+
+
+def _rplan_for(n, batch, device):
+    key = (int(n), int(batch), int(device))
+    plan = _rplans.pop(key, None)
+    if plan is None:
+        plan = TfftRealPlan(n, batch, device)
+    _rplans[key] = plan                      # (dicts keep insertion order: the first key is the least recently used)
+    while len(_rplans) > RPLAN_CACHE_SIZE:
+        _rplans.pop(next(iter(_rplans))).close()
+    return plan
+
+
+def rplan_cache_clear():
+    """Destroys the plans rfft / irfft cached."""
+    while _rplans:
+        _rplans.popitem()[1].close()
+
+
+def _is_cuda_half(t):
+    import torch
+
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float16
+
+
+def rfft(x):
+    """Half spectra of the rows of x, a CUDA float16 tensor (batch, n): (re, im), each a (batch, n/2 + 1) view into one
+    [RE h | IM h]-per-row buffer. Equals numpy.fft.rfft(x) / n (the library's sequential scaling)."""
+    import torch
+
+    if not _is_cuda_half(x) or x.dim() != 2:
+        raise TfftError(5, "rfft takes a CUDA float16 tensor of shape (batch, n)")
+    batch, n = x.shape
+    x = x.contiguous()
+    plan = _rplan_for(n, batch, x.device.index)
+    h = plan.pitch
+    out = torch.empty(batch, 2 * h, dtype=torch.float16, device=x.device)
+    flat = out.view(-1)
+    plan.r2c(x.view(-1), flat, flat[h:])
+    return out[:, :n // 2 + 1], out[:, h:h + n // 2 + 1]
+
+
+def irfft(re, im, n):
+    """Real signals (batch, n) of the half spectra re, im (CUDA float16, shape (batch, n/2 + 1)): numpy.fft.irfft(re + i im, n) under
+    the library's sequential scaling, so irfft(*rfft(x), n) = x / n. The IM of bins 0 and n/2 is ignored."""
+    import torch
+
+    n = int(n)
+    bins = n // 2 + 1
+    if not (_is_cuda_half(re) and _is_cuda_half(im)) or re.dim() != 2 or re.shape != im.shape or re.shape[1] != bins or re.device != im.device:
+        raise TfftError(5, "irfft takes two CUDA float16 tensors of shape (batch, n/2 + 1) on one device")
+    batch = re.shape[0]
+    plan = _rplan_for(n, batch, re.device.index)
+    h = plan.pitch
+    spec = torch.empty(batch, 2 * h, dtype=torch.float16, device=re.device)
+    spec[:, :bins] = re
+    spec[:, h:h + bins] = im
+    flat = spec.view(-1)
+    out = torch.empty(batch, n, dtype=torch.float16, device=re.device)
+    plan.c2r(flat, flat[h:], out.view(-1))
+    return out
 
 
 def permute_twiddle(in_re, in_im, out_re, out_im, a, b, c, n_tw=0, e0=0, stream=None):

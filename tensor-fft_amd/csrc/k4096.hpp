@@ -50,6 +50,8 @@
 #include <cstring>
 #include <vector>
 
+#include "rsplit.hpp"
+
 namespace k4096 {
 
 constexpr int kWavesPerBlock = 8;
@@ -121,6 +123,15 @@ __device__ __forceinline__ void cmul_to(float& re, float& im, const Cf w) {
 __device__ __forceinline__ void otw_apply(const OutTw& t, uint32_t row, uint32_t q, float& re, float& im) {
   cmul_to(re, im, otw_w(t, row, q));
 }
+
+// Fused R2C epilogue (RS = true, include/tfft.h tfft_rplan_*): transform b is the pair of real signals 2b, 2b + 1 read as RE and
+// IM planes (in_im = in_re + real stride, in_map stride = 2 real strides). Its spectrum Z leaves as the two half spectra of
+// rsplit.hpp: signal 2b at out_*_plane + out_map.off(b), signal 2b + 1 at + b_off, bins 0 .. 2048 each. Transform self_pair (an odd
+// batch's last signal) reads its IM plane from its RE plane and writes only the first half spectrum. Default: off.
+struct RealOut {
+  uint64_t b_off = 0;
+  uint32_t self_pair = 0xffffffffu;
+};
 
 // ---------------------------------------------------------------------------
 // host: constant operands
@@ -345,10 +356,12 @@ __device__ __forceinline__ void st(uint16_t* p, u4 v) {
 }
 
 // in_*/out_*: planar binary16; FFT b at +b*stride halves. tables: build_tables() blob.
-template <int V, bool OTW = false>
+// RS: fused R2C epilogue (RealOut above), instantiated only for V = kStageOut | kNonTemporal.
+template <int V, bool OTW = false, bool RS = false>
 __global__ __launch_bounds__(kThreads, 2) void fft4096_kernel(
     const uint16_t* in_re, const uint16_t* in_im, uint16_t* out_re, uint16_t* out_im, Addr in_map,
-    Addr out_map, uint32_t batch, uint32_t live, const uint8_t* __restrict__ tables, OutTw otw) {
+    Addr out_map, uint32_t batch, uint32_t live, const uint8_t* __restrict__ tables, OutTw otw, RealOut ro) {
+  static_assert(!RS || (V == (kStageOut | kNonTemporal) && !OTW), "the fused R2C epilogue reads the staged spectrum image");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -379,8 +392,10 @@ __global__ __launch_bounds__(kThreads, 2) void fft4096_kernel(
   // (Issuing this first copy ahead of the table fill was measured 9-20 % SLOWER at batch 65536: workgroups then start their HBM
   // reads in lock-step, profiles/r1_k4096_grid_scan.txt. Round 5 tried it again for ONE transform, where it would save a memory
   // round trip on paper: 5.5 us per transform against 4.9 in this order, 6.2 when the idle waves copied as well. Not kept.)
+  // IM plane of transform b: the RE plane itself for the self-paired last signal of an odd real batch
+  auto im_src = [&](uint32_t bb) { return (RS && bb == ro.self_pair ? in_re : in_im) + in_map.off(bb); };
   dma_in<(V & kNonTemporal) != 0>(reinterpret_cast<const uint8_t*>(in_re + in_map.off(b)),
-           reinterpret_cast<const uint8_t*>(in_im + in_map.off(b)), wl_off, lane);
+           reinterpret_cast<const uint8_t*>(im_src(b)), wl_off, lane);
 
   const uint8_t* const g_tab = lds + lane * 16;
   const uint8_t* const h_tab = lds + 16384 + lane * 16;
@@ -559,7 +574,58 @@ __global__ __launch_bounds__(kThreads, 2) void fft4096_kernel(
         }
       }
     }
-    if (V & kStageOut) {
+    if (RS) {
+      // split the image into the two half spectra (rsplit.hpp). Vector v (bins 8v .. 8v + 7) of a plane sits at byte
+      // 16 (v ^ ((v >> 3) & 1)) of the image (the slot swizzle above). Lane takes v = 64 i + lane: bins 8v + j pair with
+      // N - 8v - j, which for j = 1 .. 7 are elements 8 - j of vector 511 - v, and for j = 0 element 0 of vector (512 - v) mod 512.
+      // 256 full 16-byte vectors per plane and half spectrum, plus the Nyquist bin 2048 (element 0 of vector 256) as one half.
+      auto img = [&](uint32_t v) { return wl + 16u * (v ^ ((v >> 3) & 1u)); };
+      const bool has_b = b != ro.self_pair;
+      uint16_t* const a_re = out_re + out_map.off(b);
+      uint16_t* const a_im = out_im + out_map.off(b);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint32_t v = 64u * i + lane;
+        const u4 xr = *reinterpret_cast<const u4*>(img(v));
+        const u4 xi = *reinterpret_cast<const u4*>(img(v) + 8192);
+        const u4 yr = *reinterpret_cast<const u4*>(img(511u - v));
+        const u4 yi = *reinterpret_cast<const u4*>(img(511u - v) + 8192);
+        const uint16_t y0r = *reinterpret_cast<const uint16_t*>(img((512u - v) & 511u));
+        const uint16_t y0i = *reinterpret_cast<const uint16_t*>(img((512u - v) & 511u) + 8192);
+        uint16_t zr[8], zi[8], mr[8], mi[8];
+        __builtin_memcpy(zr, &xr, 16);
+        __builtin_memcpy(zi, &xi, 16);
+        __builtin_memcpy(mr, &yr, 16);
+        __builtin_memcpy(mi, &yi, 16);
+        uint16_t ar[8], ai[8], br[8], bi[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          rsplit::split_bin(zr[j], zi[j], j ? mr[8 - j] : y0r, j ? mi[8 - j] : y0i, ar[j], ai[j], br[j], bi[j]);
+        u4 var, vai, vbr, vbi;
+        __builtin_memcpy(&var, ar, 16);
+        __builtin_memcpy(&vai, ai, 16);
+        __builtin_memcpy(&vbr, br, 16);
+        __builtin_memcpy(&vbi, bi, 16);
+        st<V>(a_re + 8 * v, var);
+        st<V>(a_im + 8 * v, vai);
+        if (has_b) {
+          st<V>(a_re + ro.b_off + 8 * v, vbr);
+          st<V>(a_im + ro.b_off + 8 * v, vbi);
+        }
+      }
+      if (lane == 0) {
+        const uint16_t nr = *reinterpret_cast<const uint16_t*>(img(256));
+        const uint16_t ni = *reinterpret_cast<const uint16_t*>(img(256) + 8192);
+        uint16_t ar, ai, br, bi;
+        rsplit::split_bin(nr, ni, nr, ni, ar, ai, br, bi);
+        a_re[2048] = ar;
+        a_im[2048] = ai;
+        if (has_b) {
+          a_re[ro.b_off + 2048] = br;
+          a_im[ro.b_off + 2048] = bi;
+        }
+      }
+    } else if (V & kStageOut) {
       // read the image back row by row (1 KiB per wave instruction) and store it coalesced
       const uint32_t rd = 16u * (lane ^ ((lane >> 3) & 1));
 #pragma unroll
@@ -574,7 +640,7 @@ __global__ __launch_bounds__(kThreads, 2) void fft4096_kernel(
     if (!(V & kPrefetch)) {
       if (V & kStageOut) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // image read out before reuse
       dma_in<(V & kNonTemporal) != 0>(reinterpret_cast<const uint8_t*>(in_re + in_map.off(nb)),
-             reinterpret_cast<const uint8_t*>(in_im + in_map.off(nb)), wl_off, lane);
+             reinterpret_cast<const uint8_t*>(im_src(nb)), wl_off, lane);
     }
     b = nb;
   }

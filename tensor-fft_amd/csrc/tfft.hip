@@ -401,10 +401,9 @@ inline uint32_t live_waves(const tfft_plan* p, uint64_t units) {
   return 8;
 }
 
-template <int V>
-int launch_k4096_v(const tfft_plan* p, const void* in_re, const void* in_im, void* out_re, void* out_im,
-                   k4096::Addr in_stride, k4096::Addr out_stride, hipStream_t s) {
-  const uint32_t live = live_waves(p, p->batch);
+// Launch shape of the N = 4096 kernel for p->batch transforms: waves per workgroup that take work, and the grid
+inline void k4096_shape(const tfft_plan* p, uint32_t& live, uint32_t& grid) {
+  live = live_waves(p, p->batch);
   const uint32_t blocks_needed = static_cast<uint32_t>((p->batch + live - 1) / live);
   // Workgroups are sized so that each wave runs about two transforms: the second one's HBM->LDS copy flies under
   // the first one's stores, and the hardware dispatcher hands out the remaining workgroups as CUs drain, which keeps
@@ -412,20 +411,27 @@ int launch_k4096_v(const tfft_plan* p, const void* in_re, const void* in_im, voi
   // transform per wave 5.1 TB/s; profiles/r1_k4096_grid_scan.txt).
   static const uint32_t iters_env = env_iters("TFFT_K4096_ITERS", 0);   // experiment knob (debug build only)
   const uint32_t iters = iters_env ? iters_env : plan_iters(p->launch_iters, blocks_needed >= 4u * static_cast<uint32_t>(p->num_cus) ? 2u : 1u);
-  const uint32_t grid = pick_grid(blocks_needed, p->num_cus, iters);
+  grid = pick_grid(blocks_needed, p->num_cus, iters);
+}
+
+template <int V>
+int launch_k4096_v(const tfft_plan* p, const void* in_re, const void* in_im, void* out_re, void* out_im,
+                   k4096::Addr in_stride, k4096::Addr out_stride, hipStream_t s) {
+  uint32_t live, grid;
+  k4096_shape(p, live, grid);
   if constexpr (V == (k4096::kStageOut | k4096::kNonTemporal)) {
     if (p->otw.n_mask) {       // row pass of a transposed-input plan (default variant only, create_transposed_in)
       TFFT_LAUNCH((k4096::fft4096_kernel<V, true>), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
                          static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                          static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), in_stride, out_stride,
-                         static_cast<uint32_t>(p->batch), live, static_cast<const uint8_t*>(p->d_tables), p->otw);
+                         static_cast<uint32_t>(p->batch), live, static_cast<const uint8_t*>(p->d_tables), p->otw, k4096::RealOut{});
       return TFFT_OK;
     }
   }
   TFFT_LAUNCH((k4096::fft4096_kernel<V, false>), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
                      static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                      static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), in_stride, out_stride,
-                     static_cast<uint32_t>(p->batch), live, static_cast<const uint8_t*>(p->d_tables), p->otw);
+                     static_cast<uint32_t>(p->batch), live, static_cast<const uint8_t*>(p->d_tables), p->otw, k4096::RealOut{});
   return TFFT_OK;
 }
 
@@ -2276,3 +2282,4 @@ double tfft_plan_mfma_flops(const tfft_plan* p) {
 
 #include "dist.hpp"
 #include "staging.hpp"
+#include "rfft.hpp"
