@@ -2,6 +2,7 @@
 """bench.py — headline benchmark of the hot path: batched 1D N=4096 fp16 C2C FFT (BASELINE.json configs[1]).
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full    (everything else the benchmark measures and checks, see below)
     python bench.py --gpus N --steps K --warmup W          (starts its N ranks itself, see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -18,7 +19,15 @@ against the oracle's fp64 DFT/N, so a broken kernel cannot post a number.
 
 Rank 0 prints ONE JSON line. `roofline` is the HBM roofline of the dominant kernel (algorithmic bytes = 8 B per complex
 sample per launch: 4 read + 4 written) with the launch duration measured here by HIP events on the launch
-stream. `cpu_baseline` is the CPU oracle (oracle/, a port: the reference has no CPU path, its oracle is cuFFT on the GPU)
+stream over the timed steps.
+
+A plain run does only what that line's headline needs: set-up, the untimed and warm-up launches, the K timed steps, the
+--dump-outputs files, the self-check of the timed output and the line. Everything else is behind `--full` (off by default),
+which adds after the headline, outside `value`: `roofline.kernel_ms_single_launches` (20 individually timed launches),
+`cpu_baseline`, `other_configs` and the configs[4b] entry. Under `--full`, `--no-cpu-baseline` and `--no-other-configs` leave
+parts of that out again; the configs[4b] options (--with-dist and the two that go with it) need `--full`.
+
+`cpu_baseline` is the CPU oracle (oracle/, a port: the reference has no CPU path, its oracle is cuFFT on the GPU)
 timed on this host's cores on a bounded sample of the same input: fp64 radix-2 FFT/N over OpenMP (`value`) and on one
 thread, plus the fp64 naive DFT/N at N=256 (BASELINE configs[0]) and at N=4096 on a 64-transform sub-batch.
 At 1 GPU `other_configs` carries short measurements of the other BASELINE configs (2^20 x 1024 natural and transposed
@@ -653,6 +662,9 @@ def main():
     ap.add_argument("--batch", type=int, default=0,
                     help="transforms per GPU (default: 65536 = BASELINE configs[1] at 1 GPU, 2^21 = the per-GPU share of "
                          "configs[4a] at N > 1 GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: 20 individually timed launches, the CPU "
+                         "baseline, the other BASELINE configs ('other_configs') and, under N > 1 GPUs, the configs[4b] entry")
     ap.add_argument("--with-dist", action="store_true",
                     help="also run the BASELINE configs[4b] entry (N = 2^26 through tfft_dist_*) when there is only one rank")
     ap.add_argument("--dist-self-via-comm", action="store_true",
@@ -662,15 +674,19 @@ def main():
                     help="of the other_configs entries run only configs[4b] (with --with-dist on one rank: the rehearsal the GPU tests use)")
     ap.add_argument("--dist-timeout", type=float, default=300.0,
                     help="seconds the configs[4b] entry may take before the line is printed without it and the run exits with code 3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short extra measurements of the other BASELINE configs (reported under 'other_configs')")
+                    help="with --full: skip the short extra measurements of the other BASELINE configs (reported under "
+                         "'other_configs') and the configs[4b] entry")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the last one computed (rank 0's output; a fixed seeded sample of at most "
                          f"{DUMP_TRANSFORMS} transforms) as float32 DIR/out_re.npy and DIR/out_im.npy")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    for flag in ("--with-dist", "--dist-self-via-comm", "--only-dist-entry"):
+        if getattr(args, flag[2:].replace("-", "_")) and not args.full:
+            ap.error(f"{flag} is part of --full")
 
     import torch                     # (importing torch and counting devices do not initialise the GPU)
 
@@ -769,18 +785,17 @@ def main():
     # what the last timed step computed, before anything else runs on y
     dumped = dump_outputs(torch, y, N, batch, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
-    # per-launch spread (SURVEY 8d asks for mean and sigma; the true mean, not the reference's sum / (n - 1),
+    # --full: per-launch spread (SURVEY 8d asks for mean and sigma; the true mean, not the reference's sum / (n - 1),
     # BenchUtil.h:41-48): 20 individually timed launches after the timed region, not part of `value`
     singles = []
-    for _ in range(20):
-        a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a0.record()
-        step()
-        a1.record()
-        torch.cuda.synchronize()
-        singles.append(a0.elapsed_time(a1))
-    single_mean = sum(singles) / len(singles)
-    single_sigma = (sum((v - single_mean) ** 2 for v in singles) / (len(singles) - 1)) ** 0.5
+    if args.full:
+        for _ in range(20):
+            a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a0.record()
+            step()
+            a1.record()
+            torch.cuda.synchronize()
+            singles.append(a0.elapsed_time(a1))
 
     # self-check so a broken kernel cannot post a number: Parseval on every rank's first 64 transforms; on rank 0 sampled
     # transforms of the timed output against the CPU oracle's fp64 DFT/N of the regenerated input
@@ -860,12 +875,15 @@ def main():
                 "traffic_source": traffic[1] if traffic else None,
                 "kernel_ms": kernel_ms,
                 "kernel_ms_per_rank": {"min": min(kernel_ms_per_rank), "max": max(kernel_ms_per_rank), "all": kernel_ms_per_rank},
-                "kernel_ms_single_launches": {"mean": single_mean, "sigma": single_sigma, "n": len(singles)},
                 "algorithmic_bytes_per_launch": alg_bytes,
             },
             "mfma": {"tflops": mfma_tflops, "peak": MFMA_PEAK_TFLOPS, "frac": mfma_tflops / MFMA_PEAK_TFLOPS,
                      "flop_per_sample": 384},
         }
+        if singles:
+            single_mean = sum(singles) / len(singles)
+            single_sigma = (sum((v - single_mean) ** 2 for v in singles) / (len(singles) - 1)) ** 0.5
+            line["roofline"]["kernel_ms_single_launches"] = {"mean": single_mean, "sigma": single_sigma, "n": len(singles)}
         line["runtime"] = {
             "world_size": dist.get_world_size() if dist is not None else 1,
             "backend": dist.get_backend() if dist is not None else None,
@@ -877,15 +895,15 @@ def main():
         }
         if dumped is not None:
             line["dump_outputs"] = dumped
-        if world == 1 and not args.no_other_configs and not args.only_dist_entry and batch == BATCH:
+        if args.full and world == 1 and not args.no_other_configs and not args.only_dist_entry and batch == BATCH:
             x = y = None
             torch.cuda.empty_cache()
             line["other_configs"] = other_configs(torch, tf, orc, local_rank)
     else:
         line = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline()          # (before the distributed entry: everything the line needs apart from that entry is then in hand)
-    if (world > 1 or args.with_dist) and not args.no_other_configs:
+    if args.full and (world > 1 or args.with_dist) and not args.no_other_configs:
         # BASELINE configs[4b]: every rank takes part (one exchange per transform); rank 0 reports. Same failure policy as every
         # other entry ({"error": ...}, line printed, exit code non-zero), plus a watchdog: this is the one entry that contains a
         # collective no one-GPU box can rehearse with more than one rank, and a rank stuck inside it cannot be interrupted from Python.

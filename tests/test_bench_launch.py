@@ -56,6 +56,30 @@ def test_bench_gpus_2_on_a_box_without_two_gpus_fails_clearly():
     assert "needs 2 GPUs" in r.stderr and not r.stdout.strip().startswith("{")
 
 
+@pytest.mark.parametrize("flag", ["--with-dist", "--dist-self-via-comm", "--only-dist-entry"])
+def test_bench_dist_options_need_full(flag):
+    """The configs[4b] options belong to --full: without it the command is refused before anything is built or started."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", flag], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 2
+    assert f"{flag} is part of --full" in r.stderr and not r.stdout.strip()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_posts_only_the_headline():
+    """bench.py without --full: the self-checked headline line, and none of what --full adds (single launches, CPU baseline,
+    other_configs)."""
+    r = subprocess.run(["timeout", "-k", "10", "600", sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
+                        "--warmup", "1"], capture_output=True, text=True, timeout=700)
+    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "Gsamples/s" and d["dtype"] == "f16" and "rel-L2" in d["config"]["self_check"]
+    assert d["roofline"]["kernel_ms"] > 0 and "kernel_ms_single_launches" not in d["roofline"]
+    assert "cpu_baseline" not in d and "other_configs" not in d
+
+
 def test_dump_outputs_writes_a_fixed_float32_sample(tmp_path):
     """--dump-outputs on a host tensor in the output layout ([fft_i RE | fft_i IM] fp16 blocks): float32 .npy files, the same
     seeded sample of transforms in every run, the values of those transforms exactly, at most 64 MB in all."""

@@ -158,7 +158,7 @@ def test_bench_distributed_entry_rehearsal_with_one_rank():
     process group has its own RCCL communicator), the library's communicator next to it, the own chunk through ncclSend / ncclRecv.
     A fresh child with a time limit; the ONE JSON line is parsed."""
     cmd = ["timeout", "-k", "10", "900", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
-           "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--with-dist",
+           "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--with-dist",
            "--dist-self-via-comm", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--only-dist-entry"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT)

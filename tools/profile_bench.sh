@@ -16,13 +16,13 @@ mkdir -p $OUT
 # build BEFORE the first profiler line: under rocprofv3 (with --pmc its preloaded library has initialised the GPU) nothing may
 # start hipcc / make any more (that would be a wrapper hop after GPU initialisation, which this pool forbids)
 python3 -c 'import __graft_entry__ as g; g.build()'
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_${TAG}_bench -o t -- python3 bench.py --no-cpu-baseline --no-other-configs > $OUT/trace_${TAG}_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_${TAG}_bench -o t -- python3 bench.py --full --no-cpu-baseline --no-other-configs > $OUT/trace_${TAG}_bench.log 2>&1
 echo "trace done"
 i=0
 for SET in "FETCH_SIZE" "WRITE_SIZE" \
            "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VMEM"; do
   i=$((i+1))
-  rocprofv3 --pmc $SET --output-format csv -d $OUT/pmc_${TAG}_bench_$i -o p -- python3 bench.py --no-cpu-baseline --no-other-configs --steps 3 --warmup 1 > $OUT/pmc_${TAG}_bench_$i.log 2>&1
+  rocprofv3 --pmc $SET --output-format csv -d $OUT/pmc_${TAG}_bench_$i -o p -- python3 bench.py --full --no-cpu-baseline --no-other-configs --steps 3 --warmup 1 > $OUT/pmc_${TAG}_bench_$i.log 2>&1
   echo "pmc set $i done"
 done

@@ -3,7 +3,7 @@ clock ramp / warm-up executions of the profiled command) are dropped and average
 rocprofv3's own kernel_stats.csv columns, so that a roofline fraction can be recomputed from profiles/ alone.
 
     python tools/steady_stats.py "gpurun_out/trace_TAG/*kernel_trace.csv" --warmup 120 --reps 40 --out profiles/TAG_kernel_stats.csv
-    python tools/steady_stats.py TRACE --skip 320 --keep 220 ...        (bench.py: 200 cold + 100 ramp + 20 warm-up launches, then 200 timed + 20 single)
+    python tools/steady_stats.py TRACE --skip 320 --keep 220 ...        (bench.py --full: 200 cold + 100 ramp + 20 warm-up launches, then 200 timed + 20 single)
 Also prints the per-dispatch durations of the first kernel (--list N) the way tools/per_dispatch.py did."""
 import argparse
 import csv
