@@ -37,9 +37,15 @@ struct RunResults {
 
 // the knobs that exist for this length (BenchUtil.h:77-104 GetSearchSpace: what the device allows)
 std::vector<RunConfig> GetRunConfigs(long long fft_length) {
-  static const int kVariants[] = {0, 32, 524288, 8388608, 33554432, 8388608 | 33554432, 134217728, 16777216, 2097152, 268435456,
-                                  1048576, 262144, 536870912, 1073741824, 1073741824 | 8388608 | 33554432,
-                                  8388608 | 33554432 | 16777216};      // (2^15 as 256 x 128 with the cooperative radix-128 pass)
+  // bits that change the decomposition (tfft_plan_describe shows them), as opposed to kernel bits
+  constexpr int kPlannerBits = TFFT_VARIANT_AUTOSORT_ONLY | TFFT_VARIANT_NO_RADIX512 | TFFT_VARIANT_NO_RADIX1024 |
+                               TFFT_VARIANT_WIDEST_SPLIT | TFFT_VARIANT_COLUMN_PLAN | TFFT_VARIANT_NO_FUSED_TAIL;
+  constexpr int kSplit256 = TFFT_VARIANT_NO_RADIX512 | TFFT_VARIANT_NO_RADIX1024;
+  static const int kVariants[] = {0, TFFT_VARIANT_AUTOSORT_ONLY, TFFT_VARIANT_COL_WG4, TFFT_VARIANT_NO_RADIX512, TFFT_VARIANT_NO_RADIX1024,
+                                  kSplit256, TFFT_VARIANT_WIDEST_SPLIT, TFFT_VARIANT_COLUMN_PLAN, TFFT_VARIANT_NO_FUSED_TAIL,
+                                  TFFT_VARIANT_FLIP_RADIX512_KERNEL, TFFT_VARIANT_UNSTAGED_STORES, TFFT_VARIANT_COL_CACHED,
+                                  TFFT_VARIANT_COL_STREAMING, TFFT_VARIANT_NO_LATENCY_KERNEL, TFFT_VARIANT_NO_LATENCY_KERNEL | kSplit256,
+                                  kSplit256 | TFFT_VARIANT_COLUMN_PLAN};      // (2^15 as 256 x 128 with the cooperative radix-128 pass)
   static const int kIters[] = {0, 1, 2, 4, 8, TFFT_LAUNCH_PERSISTENT};
   std::vector<RunConfig> configs;
   char base[256], desc[256];
@@ -47,10 +53,9 @@ std::vector<RunConfig> GetRunConfigs(long long fft_length) {
   std::vector<std::string> seen;
   for (int v : kVariants) {
     if (tfft_variant_check(static_cast<uint64_t>(fft_length), 1, v) != TFFT_OK) continue;
-    // a planner bit that does not change this length's decomposition and no kernel bit either: the same plan again
-    const bool planner_bit = v & (32 | 8388608 | 33554432 | 134217728 | 16777216 | 2097152);
     if (tfft_plan_describe(static_cast<uint64_t>(fft_length), 1, v, desc, sizeof(desc)) != TFFT_OK) continue;
-    if (v && planner_bit && !(v & ~(32 | 8388608 | 33554432 | 134217728 | 16777216 | 2097152)) && std::string(desc) == base) continue;
+    // planner bits that do not change this length's decomposition and no kernel bit either: the same plan again
+    if (v && !(v & ~kPlannerBits) && std::string(desc) == base) continue;
     for (int it : kIters) {
       if (it && v) continue;                  // launch shapes are searched on the default kernels only
       configs.push_back(RunConfig{v, it});

@@ -122,38 +122,10 @@ typedef struct tfft_plan_opts {
                            local passes of a distributed transform) */
   int preserve_input;   /* 0: the input planes may be used as scratch, exactly as the
                            reference does (ComputeFFT.h:89-93,118-119); 1: never written */
-  int variant;          /* tuner / experiment knob, 0 = default (what tools/tuner.py writes as the sixth column).
-                           Every value accepted here yields CORRECT spectra; bits select between equivalent kernels:
-                           N == 4096 kernel: mask of 1 = prefetch the next transform under stages 2/3, 2 = stage
-                           the output through LDS (full-row stores), 8 = non-temporal loads/stores, 16 = none of
-                           these (default = 2|8; 1 and 2 exclude each other).
-                           Any N: 32 = plain autosort chain (no column kernel); 2097152 = do not fuse the
-                           radix-16 + radix-2/4 tail into one radix-32/64 pass; 8388608 = no radix-512 column
-                           passes; 33554432 = no radix-1024 column passes; 134217728 = among the splits with the
-                           fewest passes, the one with the most radix-1024 (then radix-512) passes instead of the
-                           measured default; 16777216 = N = 8192..32768 as a column plan instead of the single-pass kernel (2^15: 512 x 64; together with 8388608 | 33554432: 256 x 128 with the cooperative radix-128 final pass); 4194304 = one butterfly per thread in the radix-2/4/8 tail pass
-                           (and in the radix-64 pass of a small batch of 2^14), and the packed launch shape of the single-pass
-                           kernels (eight working waves per workgroup) for a batch that does not fill the chip, which by default
-                           spreads over the CUs with at most one working wave per SIMD (same results bit for bit).
-                           268435456 = a final radix-512 pass by the other of its two kernels: the two-round kernel
-                           (colfft512r.hpp: 128-column tiles, or 64-column tiles and two 4-wave workgroups per CU with bit
-                           524288) where the 8-wave single-round kernel is the default, and vice versa (default: two-round
-                           at row pitches of 256 and 512 columns).
-                           Column passes: 131072 = per-wave kernel, 524288 = 4-wave cooperative workgroups,
-                           262144 = plain (cached) global accesses, 536870912 = non-temporal (streaming) ones; neither:
-                           by the plan's footprint, see tfft_plan_cache_policy(); 1048576 = 16-byte stores straight from
-                           registers,
-                           4096 / 8192 = per-wave kernel with LDS-staged stores / hardware sin-cos twiddles.
-                           1073741824 = never the latency form of the radix-256 column pass (collat.hpp: one 64-column
-                           block per workgroup of 4 or 8 waves, chosen for passes of at most 64 / 128 blocks): keep the
-                           throughput kernels for such passes too (same accuracy bound; the twiddles round differently).
-                           Unknown bits are rejected (TFFT_ERR_ARG), see tfft_variant_check().
-                           Timing / debugging aids that give WRONG or partial results are NOT part of this field's
-                           accepted values: 4 and 64 (N == 4096 kernel: fake stores / no compute), (p << 8), p = 1..15 (run
-                           only the first p passes), 128 (skip inter-pass twiddles), 65536 (copy-only column pass).
-                           They are honoured only when the environment variable TFFT_DEBUG_VARIANTS=1 is set in the
-                           process that creates the plan (tools/pass_breakdown.py, tools/exp_bench.py); otherwise
-                           tfft_plan_create() refuses them, so a stale tuner file cannot produce garbage silently. */
+  int variant;          /* tuner / experiment knob, 0 = default (what tools/tuner.py writes as the sixth column): an OR of the
+                           TFFT_VARIANT_* bits below. Every accepted value yields CORRECT spectra: the bits only choose between
+                           equivalent kernels, splits and cache policies. Other bits are refused (TFFT_ERR_ARG), see
+                           tfft_variant_check(). */
   int scale;            /* TFFT_SCALE_* below; 0 = the reference's sequential scaling, result DFT(x)/N */
   int output_order;     /* TFFT_ORDER_* below; 0 = natural order */
   uint64_t fourstep_n;  /* 0 = off. Otherwise (n = 256 or 512, inner = C >= 64 columns): output row k of column c is also
@@ -175,6 +147,44 @@ typedef struct tfft_plan_opts {
                            2^16 <= N <= 2^24 (see TFFT_ORDER_* below) */
 } tfft_plan_opts;
 enum { TFFT_LAUNCH_PERSISTENT = 65535 };
+
+/* tfft_plan_opts.variant: the bits a tuner or a caller may set, alone or together. Each picks one of several kernels or splits
+ * that compute the same transform. Neither COL_CACHED nor COL_STREAMING: the column passes' cache policy follows the plan's
+ * footprint (tfft_plan_cache_policy). N = 4096 kernel: 0 = STAGE_OUT | NONTEMPORAL; PREFETCH and STAGE_OUT exclude each other, and
+ * K4096_PLAIN excludes the other three.
+ * Bits 4, 64, 128, 65536 and (p << 8), p = 1 .. 15, are timing / debugging aids that give WRONG or partial results (fake stores,
+ * no compute, no inter-pass twiddles, copy-only column passes, only the first p passes). They have no name here. This library
+ * refuses them always. Only a build with -DTFFT_DEBUG_KERNELS (libtfft_debug.so, for the measurement drivers under tools/)
+ * honours them, and only in a process with TFFT_DEBUG_VARIANTS=1 in its environment. */
+enum {
+  TFFT_VARIANT_K4096_PREFETCH = 1,            /* N = 4096: fetch the next transform under stages 2 / 3 */
+  TFFT_VARIANT_K4096_STAGE_OUT = 2,           /* N = 4096: stage the output through LDS (full-row stores) */
+  TFFT_VARIANT_K4096_NONTEMPORAL = 8,         /* N = 4096: non-temporal loads and stores */
+  TFFT_VARIANT_K4096_PLAIN = 16,              /* N = 4096: none of the three above */
+  TFFT_VARIANT_AUTOSORT_ONLY = 32,            /* any N: the plain autosort chain, no single-pass or column kernel */
+  TFFT_VARIANT_COL_WAVE_STAGED = 4096,        /* column passes: the per-wave kernel with LDS-staged stores */
+  TFFT_VARIANT_COL_WAVE_SINCOS = 8192,        /* column passes: the per-wave kernel with hardware sin / cos twiddles */
+  TFFT_VARIANT_COL_PER_WAVE = 131072,         /* column passes: the per-wave kernel, not the workgroup-cooperative ones */
+  TFFT_VARIANT_COL_CACHED = 262144,           /* column passes: plain (cached) global accesses */
+  TFFT_VARIANT_COL_WG4 = 524288,              /* column passes: 4-wave cooperative workgroups (two per CU), not one of 8 waves */
+  TFFT_VARIANT_UNSTAGED_STORES = 1048576,     /* column passes and N = 512 .. 2048: stores straight from registers */
+  TFFT_VARIANT_NO_FUSED_TAIL = 2097152,       /* no radix-16 + radix-2/4/8 tail fused into one radix-32/64/128 pass */
+  TFFT_VARIANT_PACKED = 4194304,              /* four effects: one butterfly per thread in the radix-2/4/8 tail pass; no
+                                                 workgroup-cooperative radix-32/64 final pass (small batches of 2^13 / 2^14);
+                                                 single-pass kernels: eight working waves per workgroup for a batch that does
+                                                 not fill the chip; N = 8192 .. 32768: 8 / R transforms per workgroup */
+  TFFT_VARIANT_NO_RADIX512 = 8388608,         /* no radix-512 column passes */
+  TFFT_VARIANT_COLUMN_PLAN = 16777216,        /* N = 8192 .. 32768 as a column plan (2^15: 512 x 64; with NO_RADIX512 |
+                                                 NO_RADIX1024: 256 x 128 with the cooperative radix-128 final pass) */
+  TFFT_VARIANT_NO_RADIX1024 = 33554432,       /* no radix-1024 column passes */
+  TFFT_VARIANT_RADIX512_ONE_PASS = 67108864,  /* n = 512 on a strided axis (inner >= 64) as one radix-512 column pass */
+  TFFT_VARIANT_WIDEST_SPLIT = 134217728,      /* among the splits with the fewest passes, the most radix-1024 (then radix-512) */
+  TFFT_VARIANT_FLIP_RADIX512_KERNEL = 268435456, /* a final radix-512 pass by the other of its two kernels (colfft512r.hpp's
+                                                 two-round kernel where the single-round one is the default, and vice versa;
+                                                 default: two-round at row pitches of 256 and 512 columns) */
+  TFFT_VARIANT_COL_STREAMING = 536870912,     /* column passes: non-temporal (streaming) global accesses */
+  TFFT_VARIANT_NO_LATENCY_KERNEL = 1073741824 /* no latency column kernel (collat.hpp) for passes of small work */
+};
 /* Zero-initialised options that carry the compile-time size: `tfft_plan_opts o = TFFT_PLAN_OPTS_INIT;` */
 #define TFFT_PLAN_OPTS_INIT {(uint32_t)sizeof(tfft_plan_opts)}
 /* The same at run time, for bindings that build the struct by hand (cgo, ctypes, JNI): zeroes `bytes` bytes at opts and
@@ -207,8 +217,8 @@ enum { TFFT_SCALE_SEQUENTIAL = 0, TFFT_SCALE_NONE = 1, TFFT_SCALE_ONCE = 2 };
  *                spectrum, index it through the map above, or work on it pointwise and transform back with a plan whose
  *                INPUT order is TRANSPOSED. Contiguous axis only (inner > 1 is refused). Lengths without a two-pass
  *                split fall back to NATURAL (tfft_plan_transposed_n2(n) == 0). variant: only the column-pass bits
- *                262144 / 524288 and the single-kernel bits of the N2 kernel (1 / 2 / 8 / 16, 1048576) are honoured,
- *                others are refused. Needs a workspace (tfft_plan_workspace_bytes). */
+ *                (TFFT_VARIANT_COL_CACHED / _COL_STREAMING / _COL_WG4) and the bits of the N2 kernel (the four
+ *                TFFT_VARIANT_K4096_*, TFFT_VARIANT_UNSTAGED_STORES) are honoured, others are refused. Needs a workspace (tfft_plan_workspace_bytes). */
 /*   input_order = TRANSPOSED (same N1, N2): the input block is that same [N1][N2] matrix, in[k1 * N2 + k2] = x[k1 + N1 * k2], and
  *                the result is in NATURAL order: N1 contiguous N2-point transforms whose fp32 epilogue applies the four-step
  *                twiddle w_N^(k1 q), then ONE radix-N1 column pass (decimation in time) = two passes over HBM for
@@ -216,7 +226,7 @@ enum { TFFT_SCALE_SEQUENTIAL = 0, TFFT_SCALE_NONE = 1, TFFT_SCALE_ONCE = 2 };
  *                spectra pointwise, transform back" costs 2 + 2 passes where natural order needs 3 + 3 from 2^21 on.
  *                Lengths without the layout are refused (TFFT_ERR_ARG), as are TRANSPOSED on both sides, inner > 1,
  *                TFFT_SCALE_ONCE (the plan's last fp32 multiply lies in front of its last stage) and every variant bit
- *                but the column-pass bits 262144 / 524288. The reference has neither order (nor an inverse):
+ *                but the column-pass bits (COL_CACHED / COL_STREAMING / COL_WG4). The reference has neither order (nor an inverse):
  *                src/base/TensorFFT256.cu:163-177 only comments on scaling. */
 enum { TFFT_ORDER_NATURAL = 0, TFFT_ORDER_TRANSPOSED = 1 };
 
@@ -235,13 +245,13 @@ int tfft_plan_cache_policy(uint64_t n, uint64_t inner, uint64_t batch);
  * samples) fills the chip - the splits behind variant 0 were measured at 2^30 samples per launch; (3) otherwise the bits of the
  * split with more, smaller workgroups (a single 2^20-point transform is 16 workgroups of the radix-1024 kernel on 256 CUs: 40 us;
  * as 256 x 256 x 16 with the latency column kernel it takes 18 us): 2^17 ... 2^21 up to 2^20 (2^17, 2^18) / 2^22 (2^19 ... 2^21)
- * samples per launch; 2^18 up to 2^22 samples: the other radix-512 kernel; 2^15 up to 8 transforms: 256 x 128 (8388608 |
- * 33554432 | 16777216: the latency column kernel + a workgroup-cooperative radix-128 pass, 7.3 us for one transform where the
+ * samples per launch; 2^18 up to 2^22 samples: the other radix-512 kernel; 2^15 up to 8 transforms: 256 x 128 (NO_RADIX512 |
+ * NO_RADIX1024 | COLUMN_PLAN: the latency column kernel + a workgroup-cooperative radix-128 pass, 7.3 us for one transform where the
  * single-pass kernel, one CU, takes 11.3); 2^14 / 2^13 up to 4 transforms: 256 x 64 / 256 x 32 the same way (8.4 -> 7.2, 7.6 -> 7.1 us). Measured limits:
  * profiles/r5_small_scan.txt. The
  * within-noise rules of round 4 (two 2^24, a single 2^25) are wisdom lines now (profiles/r5_TunerResults.dat), not code.
  * Independent of the variant, radix-256 column passes of at most 64 blocks (128 from a row pitch of 512 columns on) run as the
- * latency kernel (collat.hpp) unless the variant holds 1073741824.
+ * latency kernel (collat.hpp) unless the variant holds TFFT_VARIANT_NO_LATENCY_KERNEL.
  * tfft_plan_describe(n, inner, tfft_plan_default_variant(n, inner, batch), ...) is the decomposition such a plan gets. A caller
  * that names any variant bit itself gets exactly that variant. */
 int tfft_plan_default_variant(uint64_t n, uint64_t inner, uint64_t batch);

@@ -35,6 +35,28 @@ ABI_VERSION = 2                                               # TFFT_ABI_VERSION
 LAUNCH_PERSISTENT = 65535                                     # tfft_plan_opts.launch_iters
 SCALE_SEQUENTIAL, SCALE_NONE, SCALE_ONCE = 0, 1, 2           # tfft_plan_opts.scale
 ORDER_NATURAL, ORDER_TRANSPOSED = 0, 1                        # tfft_plan_opts.output_order
+# tfft_plan_opts.variant: the TFFT_VARIANT_* bits of include/tfft.h (plain ints, documented there)
+VARIANT_K4096_PREFETCH = 1
+VARIANT_K4096_STAGE_OUT = 2
+VARIANT_K4096_NONTEMPORAL = 8
+VARIANT_K4096_PLAIN = 16
+VARIANT_AUTOSORT_ONLY = 32
+VARIANT_COL_WAVE_STAGED = 4096
+VARIANT_COL_WAVE_SINCOS = 8192
+VARIANT_COL_PER_WAVE = 131072
+VARIANT_COL_CACHED = 262144
+VARIANT_COL_WG4 = 524288
+VARIANT_UNSTAGED_STORES = 1048576
+VARIANT_NO_FUSED_TAIL = 2097152
+VARIANT_PACKED = 4194304
+VARIANT_NO_RADIX512 = 8388608
+VARIANT_COLUMN_PLAN = 16777216
+VARIANT_NO_RADIX1024 = 33554432
+VARIANT_RADIX512_ONE_PASS = 67108864
+VARIANT_WIDEST_SPLIT = 134217728
+VARIANT_FLIP_RADIX512_KERNEL = 268435456
+VARIANT_COL_STREAMING = 536870912
+VARIANT_NO_LATENCY_KERNEL = 1073741824
 _SCALES = {"sequential": 0, "none": 1, "once": 2}
 _ORDERS = {"natural": 0, "transposed": 1}
 

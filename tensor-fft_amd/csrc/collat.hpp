@@ -26,8 +26,8 @@
 //   * plain (cached) global accesses: a plan this small lives in L2 / Infinity Cache (tfft.hip cache_policy; nt loads cost
 //     +0.5 us per pass at these sizes, write-through stores move the end-of-kernel write-back into the kernel and lose
 //     0.2 us, tools/lat_probe policies).
-// Selected by tfft.hip launch_col for plain / next-pass-twiddle passes of small work (variant bit
-// 1073741824 keeps the throughput kernels). Results are within the library's stated tolerance of the other forms, not
+// Selected by tfft.hip launch_col for plain / next-pass-twiddle passes of small work (TFFT_VARIANT_NO_LATENCY_KERNEL keeps the
+// throughput kernels). Results are within the library's stated tolerance of the other forms, not
 // bit-identical to them (hardware sin / cos twiddles, |error| ~ 1e-6, instead of the two-level fp32 tables).
 #pragma once
 

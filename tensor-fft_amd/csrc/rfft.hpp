@@ -189,7 +189,7 @@ inline bool rplan_fused(uint64_t n, int flags) { return n == 4096 && !(flags & T
 // Variant of the forward complex sub-plans. N = 4096: the default N = 4096 kernel (staged, non-temporal), named explicitly so that
 // plan wisdom (tfft_tuning_*) cannot give the sub-plan another decomposition: the fused launch runs that kernel with the sub-plan's
 // tables, and the two-pass path must compute the same spectra. Other n: 0, the library's default (wisdom included).
-constexpr int kVarK4096Default = 2 | 8;
+constexpr int kVarK4096Default = TFFT_VARIANT_K4096_STAGE_OUT | TFFT_VARIANT_K4096_NONTEMPORAL;
 inline int rplan_fwd_variant(uint64_t n) { return n == 4096 ? kVarK4096Default : 0; }
 
 // every argument of tfft_rplan_create that can be checked without a device; fills the strides

@@ -56,13 +56,27 @@ inline int ilog2(uint64_t x) {
   return l;
 }
 
-// ---- tfft_plan_opts.variant: which bits exist (include/tfft.h). The debugging aids give WRONG or partial results and
-// are refused unless TFFT_DEBUG_VARIANTS=1 is set in the environment of the process that creates the plan.
-constexpr int kVarK4096 = 1 | 2 | 8 | 16;
-constexpr int kVarNoLat = 1073741824;      // column passes of small work by the throughput kernels, not collat.hpp
-constexpr int kVarDebug = 4 | 64 | 128 | 65536 | (15 << 8);
-constexpr int kVarTuner = kVarK4096 | 32 | 4096 | 8192 | 131072 | 262144 | 524288 | 1048576 | 2097152 | 4194304 |
-                          8388608 | 16777216 | 33554432 | 67108864 | 134217728 | 268435456 | 536870912 | kVarNoLat;
+// ---- tfft_plan_opts.variant: the TFFT_VARIANT_* bits of include/tfft.h, and the debugging aids, which have no public name: they
+// give WRONG or partial results and are refused unless TFFT_DEBUG_VARIANTS=1 is set in the environment of the process that
+// creates the plan.
+constexpr int kDbgK4096FakeStore = 4;       // N = 4096 kernel: stores of the raw registers (k4096::kFakeStore)
+constexpr int kDbgK4096NoCompute = 64;      // N = 4096 kernel: the LDS image copied straight out (k4096::kNoCompute)
+constexpr int kDbgNoTwiddle = 128;          // column passes skip the next pass's twiddles
+constexpr int kDbgCopyOnly = 65536;         // copy-only column passes
+constexpr int kDbgPassesShift = 8;          // (p << 8), p = 1 .. 15: run only the first p passes
+constexpr int kDbgPasses = 15 << kDbgPassesShift;
+constexpr int kVarDebug = kDbgK4096FakeStore | kDbgK4096NoCompute | kDbgNoTwiddle | kDbgCopyOnly | kDbgPasses;
+constexpr int kVarK4096 = TFFT_VARIANT_K4096_PREFETCH | TFFT_VARIANT_K4096_STAGE_OUT | TFFT_VARIANT_K4096_NONTEMPORAL |
+                          TFFT_VARIANT_K4096_PLAIN;
+// any of these forces the per-wave column kernel
+constexpr int kVarColPerWave = TFFT_VARIANT_COL_PER_WAVE | TFFT_VARIANT_COL_WAVE_STAGED | TFFT_VARIANT_COL_WAVE_SINCOS;
+// what the sub-plans of a transposed-order plan honour: the column-pass bits, and (transposed output) the bits of the N2 kernel
+constexpr int kVarSubCol = TFFT_VARIANT_COL_CACHED | TFFT_VARIANT_COL_WG4 | TFFT_VARIANT_COL_STREAMING;
+constexpr int kVarSubRow = kVarK4096 | TFFT_VARIANT_UNSTAGED_STORES;
+constexpr int kVarTuner = kVarK4096 | TFFT_VARIANT_AUTOSORT_ONLY | kVarColPerWave | kVarSubCol | TFFT_VARIANT_UNSTAGED_STORES |
+                          TFFT_VARIANT_NO_FUSED_TAIL | TFFT_VARIANT_PACKED | TFFT_VARIANT_NO_RADIX512 | TFFT_VARIANT_COLUMN_PLAN |
+                          TFFT_VARIANT_NO_RADIX1024 | TFFT_VARIANT_RADIX512_ONE_PASS | TFFT_VARIANT_WIDEST_SPLIT |
+                          TFFT_VARIANT_FLIP_RADIX512_KERNEL | TFFT_VARIANT_NO_LATENCY_KERNEL;
 // The shipped libtfft.so holds NO timing-only kernel, no environment knob and no measurement hook: all of that is compiled
 // only with -DTFFT_DEBUG_KERNELS (tensor-fft_amd/libtfft_debug.so, built on demand for the drivers under tools/), and even
 // there the debugging bits need TFFT_DEBUG_VARIANTS=1 in the environment of the process that creates the plan.
@@ -200,17 +214,17 @@ inline bool single_kernel(const tfft_plan* p) {
 // Pass decomposition of a plan: pure host logic (no device needed; tfft_plan_describe exposes it to the CPU tests).
 // Single LDS-resident kernels for N = 256 .. 32768 with a contiguous axis; otherwise radix-256 / radix-512 column passes
 // first (they hand the next pass its twiddles), then radix-16 and one radix-2/4/8 autosort pass, a radix-16 + radix-2/4
-// tail fused into radix-32/64. variant bit 32 forces the plain autosort chain.
+// tail fused into radix-32/64. TFFT_VARIANT_AUTOSORT_ONLY forces the plain autosort chain.
 void plan_passes(uint64_t n, uint64_t inner, int variant, std::vector<Pass>& passes) {
   passes.clear();
   const int lg = ilog2(n);
-  const bool force_stockham = variant & 32;
+  const bool force_stockham = variant & TFFT_VARIANT_AUTOSORT_ONLY;
   if (n == 4096 && inner == 1 && !force_stockham) {
     passes.push_back(Pass{PassKind::K4096, 4096, 1, false, false, 0});
   } else if (n == 256 && inner == 1 && !force_stockham) {
     passes.push_back(Pass{PassKind::K256, 256, 1, false, false, 0});
-  } else if ((n == 8192 || n == 16384 || n == 32768) && inner == 1 && !force_stockham && !(variant & 16777216)) {
-    // one pass: R waves share a transform, radix-R step in front of the 4096 kernel's stages (variant bit 16777216:
+  } else if ((n == 8192 || n == 16384 || n == 32768) && inner == 1 && !force_stockham && !(variant & TFFT_VARIANT_COLUMN_PLAN)) {
+    // one pass: R waves share a transform, radix-R step in front of the 4096 kernel's stages (TFFT_VARIANT_COLUMN_PLAN:
     // the multi-pass column plan instead)
     passes.push_back(Pass{PassKind::K4096R, static_cast<int>(n / 4096), 1, false, false, 0});
   } else if ((n == 512 || n == 1024 || n == 2048) && inner == 1 && !force_stockham) {
@@ -231,9 +245,9 @@ void plan_passes(uint64_t n, uint64_t inner, int variant, std::vector<Pass>& pas
         {256, 256, 0},    {512, 256, 0},    {512, 512, 0},     {512, 1024, 0},     {1024, 1024, 0},      // 2^16 .. 2^20
         {512, 512, 0},    {512, 512, 0},    {512, 512, 0},     {512, 1024, 0},     {1024, 1024, 0},      // 2^21 .. 2^25
         {512, 512, 256},  {1024, 512, 256}, {256, 1024, 1024}, {1024, 512, 1024},  {1024, 1024, 1024}};  // 2^26 .. 2^30
-    const bool use512 = col_ok && inner == 1 && lg >= 15 && !(variant & 8388608);
-    const bool use1024 = col_ok && inner == 1 && lg >= 16 && !(variant & 33554432);
-    if (use512 && use1024 && lg >= 16 && lg <= 30 && !(variant & 134217728)) {
+    const bool use512 = col_ok && inner == 1 && lg >= 15 && !(variant & TFFT_VARIANT_NO_RADIX512);
+    const bool use1024 = col_ok && inner == 1 && lg >= 16 && !(variant & TFFT_VARIANT_NO_RADIX1024);
+    if (use512 && use1024 && lg >= 16 && lg <= 30 && !(variant & TFFT_VARIANT_WIDEST_SPLIT)) {
       radices.clear();
       int bits = 0;
       for (int i = 0; i < 3 && kColSplit[lg - 16][i]; ++i) {
@@ -243,9 +257,9 @@ void plan_passes(uint64_t n, uint64_t inner, int variant, std::vector<Pass>& pas
       n256 = static_cast<int>(radices.size());
       rem = lg - bits;
     } else if (use512 || use1024) {
-      // restricted variants (no radix-512: 8388608, no radix-1024: 33554432) and 2^15: the split lg = 8 a + 9 b + 10 c + t,
+      // restricted variants (TFFT_VARIANT_NO_RADIX512, TFFT_VARIANT_NO_RADIX1024) and 2^15: the split lg = 8 a + 9 b + 10 c + t,
       // t <= 7, with the fewest passes (a tail of t bits costs 0 / 1 / 2 passes for t = 0 / 1..6 / 7); ties go to the
-      // fewest radix-1024, then the fewest radix-512 passes, or with variant bit 134217728 to the most; wide radices first.
+      // fewest radix-1024, then the fewest radix-512 passes, or with TFFT_VARIANT_WIDEST_SPLIT to the most; wide radices first.
       auto tail_cost = [](int t) { return t == 0 ? 0 : (t <= 6 ? 1 : 2); };
       int best_a = n256, best_b = 0, best_c = 0, best_cost = n256 + tail_cost(rem);
       for (int c = 0; c <= (use1024 ? 3 : 0); ++c)
@@ -255,7 +269,7 @@ void plan_passes(uint64_t n, uint64_t inner, int variant, std::vector<Pass>& pas
             const int t = lg - 8 * a2 - 9 * b - 10 * c;
             if (t > 7) continue;
             const int cost = a2 + b + c + tail_cost(t);
-            const bool wide = (variant & 134217728) && cost == best_cost &&
+            const bool wide = (variant & TFFT_VARIANT_WIDEST_SPLIT) && cost == best_cost &&
                               (c > best_c || (c == best_c && b > best_b));
             if (cost < best_cost || wide) {
               best_cost = cost;
@@ -270,8 +284,8 @@ void plan_passes(uint64_t n, uint64_t inner, int variant, std::vector<Pass>& pas
       radices.insert(radices.end(), best_a, 256);
       rem = lg - 8 * best_a - 9 * best_b - 10 * best_c;
     }
-    // n = 512 along a strided axis as ONE radix-512 column pass (variant bit 67108864; the second pass of the fused 2D plan)
-    if (n == 512 && inner >= 64 && (variant & 67108864) && !force_stockham) {
+    // n = 512 along a strided axis as ONE radix-512 column pass (TFFT_VARIANT_RADIX512_ONE_PASS; the second pass of the fused 2D plan)
+    if (n == 512 && inner >= 64 && (variant & TFFT_VARIANT_RADIX512_ONE_PASS) && !force_stockham) {
       radices.assign(1, 512);
       n256 = 1;
       rem = 0;
@@ -303,8 +317,8 @@ void plan_passes(uint64_t n, uint64_t inner, int variant, std::vector<Pass>& pas
     for (; rem >= 4; rem -= 4) radices.push_back(16);
     if (rem) radices.push_back(1 << rem);
     // a radix-16 pass followed by a radix-2 / radix-4 pass behind a column pass fuses into one radix-32 / radix-64
-    // pass (the butterfly fits in registers; its input twiddles come from the column pass). variant bit 2097152 keeps them apart.
-    const bool fuse_tail = !(variant & 2097152);
+    // pass (the butterfly fits in registers; its input twiddles come from the column pass). TFFT_VARIANT_NO_FUSED_TAIL keeps them apart.
+    const bool fuse_tail = !(variant & TFFT_VARIANT_NO_FUSED_TAIL);
     if (fuse_tail && n256 >= 1 && radices.size() >= static_cast<size_t>(n256) + 2) {
       const size_t last = radices.size() - 1;
       // (... and 2^15 = 256 x 16 x 8 into 256 x 128 with the workgroup-cooperative radix-128 pass, stockham::tail_coop_kernel)
@@ -319,7 +333,7 @@ void plan_passes(uint64_t n, uint64_t inner, int variant, std::vector<Pass>& pas
       const int R = radices[i];
       const bool last = (i + 1 == radices.size());
       if (R >= 256) {
-        const bool no_tw = kDebugBuild && (variant & 128);   // debugging aid: WRONG results, timing/determinism only
+        const bool no_tw = kDebugBuild && (variant & kDbgNoTwiddle);   // debugging aid: WRONG results, timing/determinism only
         passes.push_back(Pass{PassKind::Col256, R, ns, !last && !no_tw, false, last ? 0 : radices[i + 1]});
       } else {
         const bool prev_col = i > 0 && radices[i - 1] >= 256;
@@ -392,9 +406,9 @@ inline uint32_t rounds_grid(uint64_t blocks, uint32_t capacity, uint32_t launch_
 // Waves per workgroup that take work in the single-pass kernels (one transform, or one group of transforms, per wave): 8 when the
 // batch fills the chip; for `units` wave-tasks that do not, the fewest (1, 2, 4) that still fit one workgroup per CU, so that the
 // tasks spread over the CUs with one wave per SIMD instead of filling a few CUs with two (profiles/r5_small_scan.txt, last part).
-// Variant bit 4194304 keeps the packed shape (A/B).
+// TFFT_VARIANT_PACKED keeps the packed shape (A/B).
 inline uint32_t live_waves(const tfft_plan* p, uint64_t units) {
-  if (p->variant & 4194304) return 8;
+  if (p->variant & TFFT_VARIANT_PACKED) return 8;
   const uint64_t cus = static_cast<uint64_t>(p->num_cus);
   for (uint32_t live = 1; live <= 4; live *= 2)
     if (units <= cus * live) return live;
@@ -481,7 +495,7 @@ int launch_k256r_t(const tfft_plan* p, const void* in_re, const void* in_im, voi
 
 int launch_k256r(const tfft_plan* p, int radix, const void* in_re, const void* in_im, void* out_re, void* out_im,
                  k4096::Addr in_stride, k4096::Addr out_stride, hipStream_t s) {
-  const bool direct = p->variant & 1048576;   // 8-byte stores straight from registers instead of staged full rows
+  const bool direct = p->variant & TFFT_VARIANT_UNSTAGED_STORES;   // 8-byte stores straight from registers instead of staged full rows
   switch (radix) {
     case 2:
       return direct ? launch_k256r_t<2, false>(p, in_re, in_im, out_re, out_im, in_stride, out_stride, s)
@@ -501,7 +515,7 @@ int launch_k4096r_t(const tfft_plan* p, const void* in_re, const void* in_im, vo
   // transforms per workgroup iteration: 8 / R, or ONE while that still gives every transform a CU of its own (the R waves of a
   // transform then have the SIMDs to themselves: 2^13 x 4 11.7 -> 7.6 us, 2^14 x 2 12.2 -> 8.5 us)
   const uint64_t cus = static_cast<uint64_t>(p->num_cus);
-  const uint32_t per_wg = (p->variant & 4194304) ? k4096::kWavesPerBlock / R
+  const uint32_t per_wg = (p->variant & TFFT_VARIANT_PACKED) ? k4096::kWavesPerBlock / R
                           : (R < 8 && p->batch <= cus)   ? 1u
                           : (R == 2 && p->batch <= 2 * cus) ? 2u      // (four waves: still one per SIMD)
                                                             : k4096::kWavesPerBlock / R;
@@ -564,8 +578,15 @@ int launch_rows2d(const tfft_plan* p, const void* in_re, const void* in_im, void
 int launch_k4096(const tfft_plan* p, const void* in_re, const void* in_im, void* out_re, void* out_im,
                  k4096::Addr in_stride, k4096::Addr out_stride, hipStream_t s) {
   // opts.variant: 0 = default (staged, coalesced, non-temporal stores: the fastest measured on MI355X);
-  // otherwise a mask of k4096::kPrefetch / kStageOut / kFakeStore / kNonTemporal, with 16 = "none of them".
-  const int v = (p->variant & (15 | 16 | 64)) == 0 ? (k4096::kStageOut | k4096::kNonTemporal) : (p->variant & (15 | 64));
+  // otherwise its k4096 bits are the template argument of fft4096_kernel, with TFFT_VARIANT_K4096_PLAIN = "none of them".
+  static_assert(TFFT_VARIANT_K4096_PREFETCH == k4096::kPrefetch && TFFT_VARIANT_K4096_STAGE_OUT == k4096::kStageOut &&
+                TFFT_VARIANT_K4096_NONTEMPORAL == k4096::kNonTemporal, "variant bits of the N = 4096 kernel are its template flags");
+#ifdef TFFT_DEBUG_KERNELS
+  static_assert(kDbgK4096FakeStore == k4096::kFakeStore && kDbgK4096NoCompute == k4096::kNoCompute, "debug bits of the N = 4096 kernel");
+#endif
+  constexpr int kFlags = TFFT_VARIANT_K4096_PREFETCH | TFFT_VARIANT_K4096_STAGE_OUT | TFFT_VARIANT_K4096_NONTEMPORAL |
+                         kDbgK4096FakeStore | kDbgK4096NoCompute;
+  const int v = (p->variant & (kFlags | TFFT_VARIANT_K4096_PLAIN)) == 0 ? (k4096::kStageOut | k4096::kNonTemporal) : (p->variant & kFlags);
 #define TFFT_V(N) case N: return launch_k4096_v<N>(p, in_re, in_im, out_re, out_im, in_stride, out_stride, s)
   switch (v) {
     TFFT_V(0); TFFT_V(1); TFFT_V(2); TFFT_V(8); TFFT_V(9); TFFT_V(10);
@@ -704,10 +725,10 @@ int launch_col_wg(const tfft_plan* p, int mode, int tw, int w, const colfft::Arg
     a.blk_count = static_cast<uint32_t>(g_slab.col_count / cols);
     blocks = a.blk_count;
   }
-  // non-temporal copy-in and row stores unless the plan's cache policy says plain (tfft_plan_cache_policy, variant bit 262144);
-  // columns-on-lanes form: staged full-row stores (variant bit 1048576: direct 16-byte pieces)
+  // non-temporal copy-in and row stores unless the plan's cache policy says plain (tfft_plan_cache_policy, TFFT_VARIANT_COL_CACHED);
+  // columns-on-lanes form: staged full-row stores (TFFT_VARIANT_UNSTAGED_STORES: direct 16-byte pieces)
   const bool nt = !p->plain_acc;
-  const bool stg = mode == colfft::kColsOnLanes && !(p->variant & 1048576);
+  const bool stg = mode == colfft::kColsOnLanes && !(p->variant & TFFT_VARIANT_UNSTAGED_STORES);
   const uint32_t key = col_key(kFamWg256, mode, tw, nt, w, stg);
   static const uint32_t iters_dflt = env_iters("TFFT_COLWG_ITERS", 1000000);
 #ifdef TFFT_DEBUG_KERNELS
@@ -784,7 +805,7 @@ int launch_col(const tfft_plan* p, const Pass& ps, Planes src, Planes dst, hipSt
   if (debug_variants_enabled())          // measurement hook of tools/exp_wg_end_times.py
     if (const char* e = std::getenv("TFFT_WG_TIMES_PTR"))     // (one block of 16 x 8192 words per pass of the plan)
       a.wg_times = reinterpret_cast<unsigned long long*>(std::strtoull(e, nullptr, 0)) + (&ps - &p->passes[0]) * 16 * 8192;
-  a.copy_only = (p->variant & 65536) ? 1u : 0u;
+  a.copy_only = (p->variant & kDbgCopyOnly) ? 1u : 0u;
 #endif
   a.out_row_shift = p->out_row_shift;
   a.out_sub_shift = p->out_sub_shift;
@@ -812,14 +833,14 @@ int launch_col(const tfft_plan* p, const Pass& ps, Planes src, Planes dst, hipSt
     if (a.ns_f == 1) return launch_col_row(p, col_key(fam, colfft::kColsOnLanes, ps.tw_next ? colfft::kTwNext : colfft::kTwNone, false, plain), grid, a, s);
     if (radix == 512 && p->tw4_modulus) return launch_col_row(p, col_key(fam, colfft::kColsInRegs, colfft::kTwFourStep, false, plain), grid, a, s);
     if (ps.tw_next) return launch_col_row(p, col_key(fam, colfft::kColsInRegs, colfft::kTwNext, false, plain), grid, a, s);
-    if (radix == 512 && (((a.pitch == 256 || a.pitch == 512) && a.ns_f % 128 == 0) != ((p->variant & 268435456) != 0))) {
+    if (radix == 512 && (((a.pitch == 256 || a.pitch == 512) && a.ns_f % 128 == 0) != ((p->variant & TFFT_VARIANT_FLIP_RADIX512_KERNEL) != 0))) {
       // last pass of a plan / 2D column pass by the two-round kernel (colfft512r.hpp). A/B in one process on MI355X, 8 GiB per
       // launch (profiles/r3_ab_colfft512r.txt): the 128-column two-round form is 2-4 % faster than the 8-wave single-round
       // kernel at row pitches of 256 and 512 columns (2^18 = 512 x 512: 335 -> 342 Gsamples/s) and at 2048, 2-4 % slower at
-      // 128, 1024 and 4096 (the 2D column pass); the default follows that, variant bit 268435456 flips the choice
-      // 128-column tiles (256-byte row segments, one 8-wave workgroup per CU) where the geometry allows and variant bit
-      // 524288 does not ask for 4-wave workgroups; otherwise 64-column tiles, two 4-wave workgroups per CU
-      const bool w8 = !(p->variant & 524288) && a.pitch % 128 == 0 && a.ns_f % 128 == 0;
+      // 128, 1024 and 4096 (the 2D column pass); the default follows that, TFFT_VARIANT_FLIP_RADIX512_KERNEL flips the choice
+      // 128-column tiles (256-byte row segments, one 8-wave workgroup per CU) where the geometry allows and TFFT_VARIANT_COL_WG4
+      // does not ask for 4-wave workgroups; otherwise 64-column tiles, two 4-wave workgroups per CU
+      const bool w8 = !(p->variant & TFFT_VARIANT_COL_WG4) && a.pitch % 128 == 0 && a.ns_f % 128 == 0;
       const uint32_t grid2 = gens_grid(w8 ? blocks / 2 : blocks, static_cast<uint32_t>((w8 ? 1 : 2) * p->num_cus), p->launch_iters, kGensCol8);
       return launch_col_row(p, col_key(kFam512R, w8 ? 8 : 4, sc, w8, !sc && plain), grid2, a, s);
     }
@@ -827,18 +848,18 @@ int launch_col(const tfft_plan* p, const Pass& ps, Planes src, Planes dst, hipSt
   }
   int mode, tw;
   col_mode_tw(p, ps, a, mode, tw);
-  // default: stores straight from registers (8- / 16-byte pieces); variant bit 4096: stage the output through
+  // default: stores straight from registers (8- / 16-byte pieces); TFFT_VARIANT_COL_WAVE_STAGED: stage the output through
   // LDS (16-byte coalesced stores). Measured in one process on MI355X: direct wins at 2^16 and 2^20, staging at 2^13.
-  // workgroup-cooperative form (full 256-byte row segments) whenever the geometry allows; variant bit 131072
-  // forces the per-wave kernel
-  const bool wg_allowed = !(p->variant & (131072 | 4096 | 8192));
-  // per-wave kernel: variant bit 4096 = LDS-staged stores, 8192 = twiddles from v_sin / v_cos instead of the two-level tables
-  const bool stage = p->variant & 4096, lut = !(p->variant & 8192);
+  // workgroup-cooperative form (full 256-byte row segments) whenever the geometry allows; TFFT_VARIANT_COL_PER_WAVE
+  // (or either per-wave option) forces the per-wave kernel
+  const bool wg_allowed = !(p->variant & kVarColPerWave);
+  // per-wave kernel: LDS-staged stores, and twiddles from v_sin / v_cos (TFFT_VARIANT_COL_WAVE_SINCOS) instead of the two-level tables
+  const bool stage = p->variant & TFFT_VARIANT_COL_WAVE_STAGED, lut = !(p->variant & TFFT_VARIANT_COL_WAVE_SINCOS);
   const uint64_t entries = a.tasks / a.groups;
   // narrow pitch (N = 256 pitch contiguous, columns-on-lanes form): a workgroup spans 128 / pitch whole batch
   // entries; entries that do not fill a workgroup go to the per-wave kernel in a second launch.
   // (a few entries of 64 columns, the first pass of a small batch of 2^14 = 256 x 64: the latency kernel below)
-  const bool lat_narrow = (a.pitch == 64 || a.pitch == 32) && entries <= 64 && tw != colfft::kTwFourStep && !(p->variant & kVarNoLat);
+  const bool lat_narrow = (a.pitch == 64 || a.pitch == 32) && entries <= 64 && tw != colfft::kTwFourStep && !(p->variant & TFFT_VARIANT_NO_LATENCY_KERNEL);
   if (wg_allowed && a.ns_f == 1 && a.pitch >= 16 && a.pitch < 128 && !lat_narrow) {
     const uint64_t per = 128 / a.pitch;
     const uint64_t main_entries = entries - entries % per;
@@ -860,7 +881,7 @@ int launch_col(const tfft_plan* p, const Pass& ps, Planes src, Planes dst, hipSt
   const bool wg4_ok = (a.pitch % 64 == 0) && (a.ns_f == 1 || a.ns_f % 64 == 0);
   // Work that does not fill the chip (the reference's single-transform benchmark, FFTBenchSinlge.cu): up to 64 blocks of 64
   // columns (2^20 samples per pass) -> the latency kernel (collat.hpp: one memory round trip before the block is in LDS, a column
-  // group's stage 2 split over waves on different SIMDs). Variant bit 1073741824 keeps the throughput kernels (A/B, tuner).
+  // group's stage 2 split over waves on different SIMDs). TFFT_VARIANT_NO_LATENCY_KERNEL keeps the throughput kernels (A/B, tuner).
   // Device time per execution, latency / throughput kernels (profiles/r5_small_scan.txt): 2^16 x 1: 8.8 / 14.3 us, x 16: 13.1 /
   // 16.3; 2^18 x 1 as 256 x 256 x 4: 12.8 / 18.1; 2^20 x 1: 18.4 / 22.2. Beyond 64 blocks the sign depends on the pass (2^16 x 32:
   // 20.0 / 17.7, 2^21 x 1: 26.0 / 28.7, 2^17 x 32: 26.7 / 23.3): the throughput kernels keep everything from there on. 128 blocks
@@ -871,7 +892,7 @@ int launch_col(const tfft_plan* p, const Pass& ps, Planes src, Planes dst, hipSt
   const bool lat_geom = wg4_ok || (a.pitch == 32 && a.ns_f == 1);
   // (tfft_plan_opts.launch_iters shapes the grids of the grid-stride kernels; this kernel's grid is one workgroup per block either way,
   // so a launch shape never changes WHICH kernel runs, and with it the bits: test_launch_shape_never_changes_results)
-  if (wg_allowed && lat_geom && tw != colfft::kTwFourStep && !(p->variant & kVarNoLat) && blocks64 <= (a.pitch >= 512 ? 128u : 64u)) {
+  if (wg_allowed && lat_geom && tw != colfft::kTwFourStep && !(p->variant & TFFT_VARIANT_NO_LATENCY_KERNEL) && blocks64 <= (a.pitch >= 512 ? 128u : 64u)) {
     // Workgroup shape (column groups of 16 per workgroup, waves per column group): stage 2 is bound by instruction issue, so the
     // finer the split the shorter the pass - until the row segments get too narrow for the memory system (32-byte segments over
     // 4 MiB: loads land after 2.3 us instead of 0.9, tools/lat_probe). One box, device time per transform, shapes 4 x 2 / 2 x 2 /
@@ -899,7 +920,7 @@ int launch_col(const tfft_plan* p, const Pass& ps, Planes src, Planes dst, hipSt
     return launch_col_row(p, col_key(kFamLat, mode, tw, cgs_used, hh_used, pp_used),
                           static_cast<uint32_t>(blocks16 / cgs_used) * static_cast<uint32_t>(pp_used), a, s);
   }
-  // variant bit 524288: 4-wave workgroups (two per CU) instead of one 8-wave workgroup
+  // TFFT_VARIANT_COL_WG4: 4-wave workgroups (two per CU) instead of one 8-wave workgroup
   static const uint32_t wg4_max_pitch_lanes = env_iters("TFFT_WG4_MAX_PITCH", 1024);          // experiment knobs
   // (the columns-in-registers form, whose output is staged behind two more barriers, gains from two workgroups per
   // CU up to a pitch of 16384: 2^20 x 1024 221.6 -> 228.9 Gsamples/s, 2^22 215.5 -> 220.1; beyond that the 128-byte
@@ -913,7 +934,7 @@ int launch_col(const tfft_plan* p, const Pass& ps, Planes src, Planes dst, hipSt
   const uint32_t wg4_max_pitch = (a.ns_f == 1) ? wg4_max_pitch_lanes : wg4_regs;
   // ... also when 8-wave workgroups would leave CUs idle (single long transforms: 2^20 x 1 is 32 blocks of 128 columns)
   const bool few_blocks = entries * a.pitch / 128 < static_cast<uint64_t>(p->num_cus);
-  if (wg_allowed && wg4_ok && ((p->variant & 524288) || !wg8_ok || a.pitch <= wg4_max_pitch || few_blocks))
+  if (wg_allowed && wg4_ok && ((p->variant & TFFT_VARIANT_COL_WG4) || !wg8_ok || a.pitch <= wg4_max_pitch || few_blocks))
     return launch_col_wg(p, mode, tw, 4, a, s);
   if (wg_allowed && wg8_ok) return launch_col_wg(p, mode, tw, 8, a, s);
   return launch_col_wave(p, mode, tw, stage, lut, a, s);
@@ -957,8 +978,8 @@ void launch_stockham_pass(const tfft_plan* p, const Pass& ps, Planes src, Planes
   a.scale = ps.scale;
   // pre-twiddled radix-2/4/8 pass with an even sub-transform length: two butterflies per thread, 4-byte accesses
   // (measured +5 % on the whole 2^17 transform; for radix 16 it is neutral in 1D and -6 % on the 2D column pass, so
-  // those keep one butterfly per thread). variant bit 4194304 keeps the one-butterfly kernel.
-  if (a.skip_tw && a.ns >= 2 && a.m_f >= 2 && R <= 8 && !(p->variant & 4194304)) {
+  // those keep one butterfly per thread). TFFT_VARIANT_PACKED keeps the one-butterfly kernel.
+  if (a.skip_tw && a.ns >= 2 && a.m_f >= 2 && R <= 8 && !(p->variant & TFFT_VARIANT_PACKED)) {
     switch (R) {
       case 2: launch_pass_pair<2>(a, p->batch, s); return;
       case 4: launch_pass_pair<4>(a, p->batch, s); return;
@@ -969,7 +990,7 @@ void launch_stockham_pass(const tfft_plan* p, const Pass& ps, Planes src, Planes
   // radix 64 / 32 for the last pass of 2^14 = 256 x 64 / 2^13 = 256 x 32 while the batch is small (16-byte row segments: a large batch keeps the
   // butterfly-per-thread kernel, whose accesses are whole lines)
   const bool coop_geom = a.skip_tw && a.ns == a.m_f && a.m_f % stockham::kCoopCols == 0 && p->inner == 1;
-  if (R == 128 || ((R == 64 || R == 32) && coop_geom && p->n == 256ull * R && p->batch <= 16 && !(p->variant & 4194304))) {
+  if (R == 128 || ((R == 64 || R == 32) && coop_geom && p->n == 256ull * R && p->batch <= 16 && !(p->variant & TFFT_VARIANT_PACKED))) {
     if (!coop_geom) {
       (void)fail(TFFT_ERR_ARG, "internal error: radix-128 pass outside its geometry");
       return;
@@ -1044,7 +1065,7 @@ int launch_chain(const tfft_plan* p, const void* in_re, const void* in_im, void*
     return TFFT_OK;
   }
   int np = static_cast<int>(p->passes.size());
-  if (kDebugBuild && ((p->variant >> 8) & 15)) np = std::min(np, (p->variant >> 8) & 15);   // debugging aid: run only the first passes
+  if (kDebugBuild && (p->variant & kDbgPasses)) np = std::min(np, (p->variant & kDbgPasses) >> kDbgPassesShift);   // debugging aid: run only the first passes
   if (single_kernel(p)) {
     const PassKind kind = p->passes[0].kind;
     const int rc = kind == PassKind::K4096
@@ -1151,10 +1172,10 @@ int check_variant(uint64_t n, uint64_t inner, int variant) {
                                   (kDebugBuild ? std::string("; set TFFT_DEBUG_VARIANTS=1 to allow it")
                                                : std::string("; this library holds no such kernels (they exist only in a "
                                                              "-DTFFT_DEBUG_KERNELS build, libtfft_debug.so, with TFFT_DEBUG_VARIANTS=1)")));
-  if (n == 4096 && inner <= 1 && !(variant & 32)) {
-    const int v = variant & 15;
-    if ((variant & 16) && v) return fail(TFFT_ERR_ARG, "variant bit 16 (plain N = 4096 kernel) excludes bits 1, 2, 8");
-    if ((v & 1) && (v & 2)) return fail(TFFT_ERR_ARG, "variant bits 1 (prefetch) and 2 (staged stores) of the N = 4096 kernel exclude each other");
+  if (n == 4096 && inner <= 1 && !(variant & TFFT_VARIANT_AUTOSORT_ONLY)) {
+    const int v = variant & (TFFT_VARIANT_K4096_PREFETCH | TFFT_VARIANT_K4096_STAGE_OUT | TFFT_VARIANT_K4096_NONTEMPORAL | kDbgK4096FakeStore);
+    if ((variant & TFFT_VARIANT_K4096_PLAIN) && v) return fail(TFFT_ERR_ARG, "variant bit 16 (plain N = 4096 kernel) excludes bits 1, 2, 8");
+    if ((v & TFFT_VARIANT_K4096_PREFETCH) && (v & TFFT_VARIANT_K4096_STAGE_OUT)) return fail(TFFT_ERR_ARG, "variant bits 1 (prefetch) and 2 (staged stores) of the N = 4096 kernel exclude each other");
   }
   return TFFT_OK;
 }
@@ -1363,19 +1384,19 @@ inline int small_work_variant(uint64_t n, uint64_t inner, uint64_t batch) {
   if (inner != 1 || !is_pow2(n) || batch == 0 || batch > (1ull << 30)) return 0;
   const int lg = ilog2(n);
   const uint64_t work = n * batch;
-  constexpr int kSplit256 = 8388608 | 33554432;          // no radix-512 / radix-1024 passes: 256 x 256 x R
+  constexpr int kSplit256 = TFFT_VARIANT_NO_RADIX512 | TFFT_VARIANT_NO_RADIX1024;     // 256 x 256 x R
   // 2^15 up to 8 transforms: 256 x 128 on the latency column kernel + the cooperative radix-128 pass instead of the single-pass
   // kernel, whose eight 4096-point sub-transforms share ONE CU (profiles/r5_small_scan.txt, last part: x 1: 12.0 -> 7.9 us, x 4:
   // 12.2 -> 8.8, x 8: 12.3 -> 10.3, x 16: 12.3 against 14.6)
-  if (lg == 15) return work <= (1ull << 18) ? (kSplit256 | 16777216) : 0;
+  if (lg == 15) return work <= (1ull << 18) ? (kSplit256 | TFFT_VARIANT_COLUMN_PLAN) : 0;
   // 2^14 up to 4 transforms: 256 x 64, the same two launches with the cooperative radix-64 pass (x 1: 8.4 -> 7.2 us, x 4: 8.7 -> 7.5,
   // x 8: 8.6 / 8.3, x 16: 8.8 against 9.9). 2^13 up to 4 transforms: 256 x 32 likewise (x 1: 7.6 -> 7.1 us, x 4: 7.8 -> 7.2, x 8: 7.8 /
   // 7.5, x 16: 7.8 against 8.2).
-  if (lg == 14) return work <= (1ull << 16) ? (kSplit256 | 16777216) : 0;
-  if (lg == 13) return work <= (1ull << 15) ? (kSplit256 | 16777216) : 0;
+  if (lg == 14) return work <= (1ull << 16) ? (kSplit256 | TFFT_VARIANT_COLUMN_PLAN) : 0;
+  if (lg == 13) return work <= (1ull << 15) ? (kSplit256 | TFFT_VARIANT_COLUMN_PLAN) : 0;
   if (lg < 17 || lg > 21) return 0;
   if (work <= (lg <= 18 ? (1ull << 20) : (1ull << 22))) return kSplit256;
-  if (lg == 18 && work <= (1ull << 22)) return 268435456;  // 512 x 512 with the single-round radix-512 kernel last (round 4: x 16: 32.5 -> 28.4 us)
+  if (lg == 18 && work <= (1ull << 22)) return TFFT_VARIANT_FLIP_RADIX512_KERNEL;  // 512 x 512 with the single-round radix-512 kernel last (round 4: x 16: 32.5 -> 28.4 us)
   return 0;
 }
 
@@ -1410,12 +1431,12 @@ int create_transposed(tfft_plan* p, const tfft_plan_opts* opts, int device_id) {
   co.preserve_input = 1;
   // tuner bits: the column-pass bits go to the column sub-plan, the single-kernel bits of the N2 kernel to the row sub-plan;
   // everything else has no meaning for this plan shape and is refused instead of being dropped silently
-  constexpr int kColBits = 262144 | 524288 | 536870912, kRowBits = kVarK4096 | 1048576;
-  if (p->variant & ~(kColBits | kRowBits))
+  if (p->variant & ~(kVarSubCol | kVarSubRow))
     return fail(TFFT_ERR_ARG, "tfft_plan_opts.variant " + std::to_string(p->variant) + ": a TFFT_ORDER_TRANSPOSED plan honours only the "
                               "column-pass bits 262144 / 524288 / 536870912 and the single-kernel bits 1 / 2 / 8 / 16 / 1048576");
-  co.variant = (p->variant & kColBits) | (n1 == 512 ? 67108864 : 0);
-  if (!(p->variant & (262144 | 536870912)) && footprint_policy(n * transposed_chunk(n, p->batch, false), 128)) co.variant |= 262144;
+  co.variant = (p->variant & kVarSubCol) | (n1 == 512 ? TFFT_VARIANT_RADIX512_ONE_PASS : 0);
+  if (!(p->variant & (TFFT_VARIANT_COL_CACHED | TFFT_VARIANT_COL_STREAMING)) && footprint_policy(n * transposed_chunk(n, p->batch, false), 128))
+    co.variant |= TFFT_VARIANT_COL_CACHED;
   co.scale = mode == TFFT_SCALE_SEQUENTIAL ? TFFT_SCALE_SEQUENTIAL : TFFT_SCALE_NONE;
   co.fourstep_n = n;
   co.launch_iters = p->launch_iters;
@@ -1430,7 +1451,7 @@ int create_transposed(tfft_plan* p, const tfft_plan_opts* opts, int device_id) {
   ro.preserve_input = 1;
   ro.scale = mode;
   ro.launch_iters = p->launch_iters;
-  ro.variant = p->variant & ((n2 == 4096 ? kVarK4096 : 0) | ((n2 == 512 || n2 == 1024 || n2 == 2048) ? 1048576 : 0));
+  ro.variant = p->variant & ((n2 == 4096 ? kVarK4096 : 0) | ((n2 == 512 || n2 == 1024 || n2 == 2048) ? TFFT_VARIANT_UNSTAGED_STORES : 0));
   InternalOpts ri;
   ri.group_shift = static_cast<uint32_t>(ilog2(n1));
   ri.in_gstride = n;                       // planar workspace: row b at b * N2 either way
@@ -1477,8 +1498,7 @@ int create_transposed_in(tfft_plan* p, int device_id) {
   if (p->scale_mode == TFFT_SCALE_ONCE)
     return fail(TFFT_ERR_ARG, "TFFT_SCALE_ONCE is not available with transposed-order input: the plan's last fp32 multiply lies in "
                               "front of its last stage (use TFFT_SCALE_SEQUENTIAL or TFFT_SCALE_NONE)");
-  constexpr int kColBits = 262144 | 524288 | 536870912;
-  if (p->variant & ~kColBits)
+  if (p->variant & ~kVarSubCol)
     return fail(TFFT_ERR_ARG, "tfft_plan_opts.variant " + std::to_string(p->variant) + ": a plan with transposed-order input honours only the "
                               "column-pass bits 262144 / 524288 / 536870912");
   tfft_plan_opts ro = TFFT_PLAN_OPTS_INIT;
@@ -1504,7 +1524,7 @@ int create_transposed_in(tfft_plan* p, int device_id) {
   co.preserve_input = 1;
   co.scale = p->scale_mode;
   co.launch_iters = p->launch_iters;
-  co.variant = (p->variant & kColBits) | (n1 == 512 ? 67108864 : 0);
+  co.variant = (p->variant & kVarSubCol) | (n1 == 512 ? TFFT_VARIANT_RADIX512_ONE_PASS : 0);
   rc = create_plan(n1, p->chunk, device_id, &co, InternalOpts{}, &p->sub_col);
   if (rc == TFFT_OK && tail) rc = create_plan(n1, tail, device_id, &co, InternalOpts{}, &p->sub_col_tail);
   if (rc) return rc;
@@ -1558,7 +1578,7 @@ int create_plan(uint64_t n, uint64_t batch, int device_id, const tfft_plan_opts*
     if (order == TFFT_ORDER_TRANSPOSED) return fail(TFFT_ERR_ARG, "fourstep_n and TFFT_ORDER_TRANSPOSED exclude each other");
   }
   int pvariant = opts ? opts->variant : 0;
-  if (tw4 && n == 512) pvariant |= 67108864;    // one radix-512 pass
+  if (tw4 && n == 512) pvariant |= TFFT_VARIANT_RADIX512_ONE_PASS;
   // the default plan of a caller-facing, natural-order transform that does not fill the chip: the split with more workgroups
   // (caller-facing: not a sub-plan with grouped / segmented addressing or a fused epilogue: those keep what they were tuned with)
 #ifdef TFFT_SUBPLAN_POLICY   // A/B knob: the footprint cache policy for sub-plans too
@@ -1582,7 +1602,7 @@ int create_plan(uint64_t n, uint64_t batch, int device_id, const tfft_plan_opts*
   if (pvariant == 0 && plannable) pvariant = small_work_variant(n, inner, batch);
   int rc = check_variant(n, inner, pvariant);
   if (rc) return rc;
-  if (tw4 && (pvariant & (32 | 131072 | 4096 | 8192)))
+  if (tw4 && (pvariant & (TFFT_VARIANT_AUTOSORT_ONLY | kVarColPerWave)))
     return fail(TFFT_ERR_ARG, "fourstep_n needs the workgroup-cooperative column kernels (variant bits 32, 4096, 8192, 131072 exclude it)");
   rc = tfft_device_check(device_id);
   if (rc) return rc;
@@ -1600,11 +1620,11 @@ int create_plan(uint64_t n, uint64_t batch, int device_id, const tfft_plan_opts*
   p->variant = pvariant;
   p->launch_iters = launch_iters;
   p->scale_mode = scale_mode;
-  // cache policy of the column passes: variant bit 262144 = plain accesses, 536870912 = non-temporal (streaming) accesses,
-  // neither = by the plan's footprint (cache_policy)
+  // cache policy of the column passes: TFFT_VARIANT_COL_CACHED = plain accesses, TFFT_VARIANT_COL_STREAMING = non-temporal
+  // (streaming) accesses, neither = by the plan's footprint (cache_policy)
   // (also for the row transforms of a distributed transform, the segmented-input sub-plan: 2^26 over 8 ranks, 2^18 x 32 rows per
   // rank, local work 65.4 -> 59.6 us on one box, profiles/r4_dist_local_work.txt)
-  p->plain_acc = (pvariant & 262144) ? true : ((pvariant & 536870912) ? false : ((caller_facing || io.in_seg_len != 0 || kSubplanPolicy) && cache_policy(n, inner, batch)));
+  p->plain_acc = (pvariant & TFFT_VARIANT_COL_CACHED) ? true : ((pvariant & TFFT_VARIANT_COL_STREAMING) ? false : ((caller_facing || io.in_seg_len != 0 || kSubplanPolicy) && cache_policy(n, inner, batch)));
   p->tw4_modulus = tw4;
   p->tw4_col0 = opts ? opts->fourstep_col0 : 0;
   p->in_map = k4096::Addr{in_stride, io.group_shift ? io.in_gstride : in_stride, io.group_shift, (1u << io.group_shift) - 1u};
@@ -1656,7 +1676,7 @@ int create_plan(uint64_t n, uint64_t batch, int device_id, const tfft_plan_opts*
     const Pass& f = p->passes[0];
     const uint64_t pitch = f.kind == PassKind::Col256 ? n / static_cast<uint64_t>(f.radix) : 0;
     const bool ok = inner == 1 && p->passes.size() >= 2 && p->preserve_input && f.kind == PassKind::Col256 &&
-                    (f.radix == 256 || f.radix == 512) && pitch % 128 == 0 && !(pvariant & (131072 | 4096 | 8192)) &&
+                    (f.radix == 256 || f.radix == 512) && pitch % 128 == 0 && !(pvariant & kVarColPerWave) &&
                     is_pow2(io.in_seg_len) && io.in_seg_len >= pitch && io.in_seg_len < n && io.in_seg_stride >= io.in_seg_len;
     if (!ok) return bail(fail(TFFT_ERR_ARG, "segmented input: this length does not start with a cooperative radix-256 / radix-512 column pass "
                                             "whose rows fit the segments"));
@@ -2001,8 +2021,8 @@ int tfft_plan2d_create(uint64_t rows, uint64_t cols, uint64_t batch, int device_
       co.in_batch_stride = 512 * cols;
       co.out_batch_stride = rows * cols;
       co.inner = cols;
-      co.variant = 67108864;
-#ifdef TFFT_2D_COL_VARIANT     // A/B knob: cache-policy bits (262144 / 536870912) for the column pass
+      co.variant = TFFT_VARIANT_RADIX512_ONE_PASS;
+#ifdef TFFT_2D_COL_VARIANT     // A/B knob: cache-policy bits (TFFT_VARIANT_COL_CACHED / _COL_STREAMING) for the column pass
       co.variant |= TFFT_2D_COL_VARIANT;
 #endif
 #ifdef TFFT_2D_COL_ITERS       // A/B knob: rounds per workgroup of the column pass (default: the static partition for a chunk)

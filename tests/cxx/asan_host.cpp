@@ -8,9 +8,11 @@
 int main() {
   char buf[64];
   int bad = 0;
+  const int variants[] = {0, TFFT_VARIANT_AUTOSORT_ONLY, TFFT_VARIANT_NO_RADIX512, TFFT_VARIANT_NO_RADIX1024, TFFT_VARIANT_WIDEST_SPLIT,
+                          TFFT_VARIANT_COLUMN_PLAN, TFFT_VARIANT_NO_FUSED_TAIL, TFFT_VARIANT_FLIP_RADIX512_KERNEL};
   for (int lg = 1; lg <= 30; ++lg)
     for (uint64_t inner : {1ull, 8ull, 16ull, 64ull, 4096ull})
-      for (int v : {0, 32, 8388608, 33554432, 134217728, 16777216, 2097152, 268435456}) {
+      for (int v : variants) {
         char big[256];
         const int rc = tfft_plan_describe(1ull << lg, inner, v, big, sizeof(big));
         if (rc != TFFT_OK && rc != TFFT_ERR_ARG) ++bad;

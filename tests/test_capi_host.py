@@ -124,7 +124,9 @@ def test_planner_decompositions_multiply_to_n():
     for lg in range(1, 31):
         n = 1 << lg
         for inner in (1, 8, 16, 64, 4096):
-            for variant in (0, 32, 8388608, 33554432, 8388608 | 33554432, 134217728, 16777216, 2097152, 16777216 | 8388608):
+            for variant in (0, capi.VARIANT_AUTOSORT_ONLY, capi.VARIANT_NO_RADIX512, capi.VARIANT_NO_RADIX1024,
+                            capi.VARIANT_NO_RADIX512 | capi.VARIANT_NO_RADIX1024, capi.VARIANT_WIDEST_SPLIT, capi.VARIANT_COLUMN_PLAN,
+                            capi.VARIANT_NO_FUSED_TAIL, capi.VARIANT_COLUMN_PLAN | capi.VARIANT_NO_RADIX512):
                 d = tf.plan_describe(n, inner, variant)
                 toks = d.split()
                 rad = _radices(d)
@@ -159,16 +161,16 @@ def test_planner_pass_counts():
     assert tf.plan_describe(1 << 16) == "col:256+tw col:256"
     assert tf.plan_describe(1 << 19) == "col:512+tw col:1024"
     assert tf.plan_describe(1 << 20) == "col:1024+tw col:1024"
-    assert tf.plan_describe(1 << 20, 1, 33554432) == "col:256+tw col:256+tw autosort:16-tw"
+    assert tf.plan_describe(1 << 20, 1, capi.VARIANT_NO_RADIX1024) == "col:256+tw col:256+tw autosort:16-tw"
     assert tf.plan_describe(1 << 28) == "col:256+tw col:1024+tw col:1024"
-    assert tf.plan_describe(1 << 28, 1, 134217728) == "col:1024+tw col:1024+tw col:256"
-    assert tf.plan_describe(1 << 27, 1, 33554432) == "col:512+tw col:512+tw col:512"
+    assert tf.plan_describe(1 << 28, 1, capi.VARIANT_WIDEST_SPLIT) == "col:1024+tw col:1024+tw col:256"
+    assert tf.plan_describe(1 << 27, 1, capi.VARIANT_NO_RADIX1024) == "col:512+tw col:512+tw col:512"
     assert tf.plan_describe(1 << 26) == "col:512+tw col:512+tw col:256"
     assert tf.plan_describe(1 << 21) == "col:512+tw col:512+tw autosort:8-tw"
     assert tf.plan_describe(4096, 4096) == "col:256+tw autosort:16-tw"          # 2D column pass (general shapes)
-    assert tf.plan_describe(512, 4096, 67108864) == "col:512"                    # second pass of the fused 4096^2 plan
-    assert tf.plan_describe(1 << 13, 1, 16777216) == "col:256+tw autosort:32-tw"
-    assert tf.plan_describe(1 << 16, 1, 32) == "autosort:16 autosort:16 autosort:16 autosort:16"
+    assert tf.plan_describe(512, 4096, capi.VARIANT_RADIX512_ONE_PASS) == "col:512"         # second pass of the fused 4096^2 plan
+    assert tf.plan_describe(1 << 13, 1, capi.VARIANT_COLUMN_PLAN) == "col:256+tw autosort:32-tw"
+    assert tf.plan_describe(1 << 16, 1, capi.VARIANT_AUTOSORT_ONLY) == "autosort:16 autosort:16 autosort:16 autosort:16"
     with pytest.raises(tf.TfftError):
         tf.plan_describe(3000)
 
@@ -176,14 +178,23 @@ def test_planner_pass_counts():
 
 # ---- tfft_plan_opts.variant: only documented, CORRECT-result values pass (a stale tuner file must not
 # ---- select a timing-only kernel silently)
-DEBUG_VARIANTS = [4, 64, 128, 65536, 1 << 8, 3 << 8, 15 << 8, 4 | 8, 64 | 8, 524288 | 128]
-TUNER_VARIANTS = [0, 1, 2, 8, 9, 10, 16, 32, 4096, 8192, 131072, 262144, 524288, 1048576, 2097152, 4194304, 8388608,
-                  16777216, 16777216 | 8388608, 33554432, 8388608 | 33554432, 134217728, 268435456, 536870912, 1073741824,
-                  1073741824 | 8388608 | 33554432]
+# (the debugging bits have no public name: 4, 64 = N = 4096 kernel timing forms, 128, 65536, p << 8)
+_NT = capi.VARIANT_K4096_NONTEMPORAL
+_SPLIT256 = capi.VARIANT_NO_RADIX512 | capi.VARIANT_NO_RADIX1024
+DEBUG_VARIANTS = [4, 64, 128, 65536, 1 << 8, 3 << 8, 15 << 8, 4 | _NT, 64 | _NT, capi.VARIANT_COL_WG4 | 128]
+TUNER_VARIANTS = [0, capi.VARIANT_K4096_PREFETCH, capi.VARIANT_K4096_STAGE_OUT, _NT, capi.VARIANT_K4096_PREFETCH | _NT,
+                  capi.VARIANT_K4096_STAGE_OUT | _NT, capi.VARIANT_K4096_PLAIN, capi.VARIANT_AUTOSORT_ONLY,
+                  capi.VARIANT_COL_WAVE_STAGED, capi.VARIANT_COL_WAVE_SINCOS, capi.VARIANT_COL_PER_WAVE, capi.VARIANT_COL_CACHED,
+                  capi.VARIANT_COL_WG4, capi.VARIANT_UNSTAGED_STORES, capi.VARIANT_NO_FUSED_TAIL, capi.VARIANT_PACKED,
+                  capi.VARIANT_NO_RADIX512, capi.VARIANT_COLUMN_PLAN, capi.VARIANT_COLUMN_PLAN | capi.VARIANT_NO_RADIX512,
+                  capi.VARIANT_NO_RADIX1024, _SPLIT256, capi.VARIANT_WIDEST_SPLIT, capi.VARIANT_FLIP_RADIX512_KERNEL,
+                  capi.VARIANT_COL_STREAMING, capi.VARIANT_NO_LATENCY_KERNEL, capi.VARIANT_NO_LATENCY_KERNEL | _SPLIT256,
+                  capi.VARIANT_RADIX512_ONE_PASS]
 
 
 def test_variant_check_refuses_debug_and_unknown_bits(monkeypatch):
     monkeypatch.delenv("TFFT_DEBUG_VARIANTS", raising=False)
+    assert {v for k, v in vars(capi).items() if k.startswith("VARIANT_")} <= set(TUNER_VARIANTS)     # every named bit, alone
     for n in (256, 4096, 8192, 1 << 16, 1 << 20):
         for v in TUNER_VARIANTS:
             capi.variant_check(n, 1, v)
@@ -197,7 +208,8 @@ def test_variant_check_refuses_debug_and_unknown_bits(monkeypatch):
             with pytest.raises(tf.TfftError) as e:
                 capi.variant_check(n, 1, v)
             assert "unknown" in e.value.message
-    for v in (3, 11, 16 | 2, 16 | 8):                       # N = 4096 kernel: combinations without a compiled kernel
+    pre, stg, plain = capi.VARIANT_K4096_PREFETCH, capi.VARIANT_K4096_STAGE_OUT, capi.VARIANT_K4096_PLAIN
+    for v in (pre | stg, pre | stg | _NT, plain | stg, plain | _NT):    # N = 4096 kernel: combinations without a compiled kernel
         with pytest.raises(tf.TfftError):
             capi.variant_check(4096, 1, v)
     # the shipped library holds no timing-only kernels at all (they are compiled only into libtfft_debug.so, which the
@@ -218,7 +230,7 @@ def test_tuner_file_with_unusable_variant_is_refused(tmp_path, capsys, monkeypat
     assert tf.CreatePlan(262144, str(f)) is None
     assert tf.CreatePlan(131072, str(f)) is None                    # not a variant at all
     assert "unusable kernel variant" in capsys.readouterr().out
-    assert tf.CreatePlan(1 << 20, str(f))._variant == 524288
+    assert tf.CreatePlan(1 << 20, str(f))._variant == capi.VARIANT_COL_WG4
 
 
 def test_every_committed_tuner_file_holds_only_accepted_variants(monkeypatch):

@@ -5,6 +5,8 @@ outliers at one output index of the radix-256 column pass, invisible to rel-L2 c
 import numpy as np
 import pytest
 
+from tensor_fft_amd import capi
+
 pytestmark = pytest.mark.gpu
 
 
@@ -19,8 +21,8 @@ def test_repeated_runs_are_bit_identical(n, batch, inner):
 
 @pytest.mark.parametrize("n,batch", [(1 << 13, 515), (1 << 14, 255), (1 << 15, 64)])
 def test_repeated_runs_of_the_column_plan_are_bit_identical(n, batch):
-    """2^13..2^15 default to the single-pass kernel; variant bit 16777216 selects the column-pass plan they used before."""
-    _repeat(n, batch, 1, 16777216)
+    """2^13..2^15 default to the single-pass kernel; COLUMN_PLAN selects the column-pass plan they used before."""
+    _repeat(n, batch, 1, capi.VARIANT_COLUMN_PLAN)
 
 
 @pytest.mark.parametrize("n,batch", [(1 << 16, 64), (1 << 20, 8), (1 << 21, 4), (1 << 24, 1)])

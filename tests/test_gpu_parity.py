@@ -13,6 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tensor_fft_amd import capi
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -335,15 +337,16 @@ def test_generic_lengths(tf, torch, orc, lg):
 @pytest.mark.parametrize("n,batch", [(8192, 4), (8192, 5), (8192, 7), (8192, 64), (16384, 2), (16384, 3), (16384, 9)])
 def test_narrow_pitch_cooperative_column_pass(tf, torch, orc, n, batch):
     """N = 2^13 / 2^14: the radix-256 column pass has only 32 / 64 columns; a workgroup takes 4 / 2 whole
-    transforms (contiguous rows); a ragged remainder goes to a second launch. Must equal the per-wave kernel (variant bit 131072)
+    transforms (contiguous rows); a ragged remainder goes to a second launch. Must equal the per-wave kernel (COL_PER_WAVE)
     bit for bit, and the oracle within tolerance."""
     rng = np.random.default_rng(n + batch)
     re = rng.uniform(-1, 1, (batch, n)).astype(np.float16)
     im = rng.uniform(-1, 1, (batch, n)).astype(np.float16)
-    # the column plan (default is the single-pass kernel), on the throughput kernels (1073741824: a small batch of 2^14 would take
-    # the latency column kernel since round 5, whose hardware sin / cos twiddles round differently)
-    gr, gi = _run(tf, torch, re, im, variant=16777216 | 1073741824)
-    pr, pi = _run(tf, torch, re, im, variant=16777216 | 1073741824 | 131072)
+    # the column plan (default is the single-pass kernel), on the throughput kernels (NO_LATENCY_KERNEL: a small batch of 2^14 would
+    # take the latency column kernel since round 5, whose hardware sin / cos twiddles round differently)
+    v = capi.VARIANT_COLUMN_PLAN | capi.VARIANT_NO_LATENCY_KERNEL
+    gr, gi = _run(tf, torch, re, im, variant=v)
+    pr, pi = _run(tf, torch, re, im, variant=v | capi.VARIANT_COL_PER_WAVE)
     assert np.array_equal(gr.view(np.uint16), pr.view(np.uint16)) and np.array_equal(gi.view(np.uint16), pi.view(np.uint16))
     _check_against_oracle(orc, re, im, gr, gi, mode=orc.MODE_256)
 
@@ -357,8 +360,8 @@ def test_n4096r_single_pass_kernel(tf, torch, orc, n, batch):
     re = rng.uniform(-1, 1, (batch, n)).astype(np.float16)
     im = rng.uniform(-1, 1, (batch, n)).astype(np.float16)
     # (round 5: up to 8 transforms of 2^15 default to the two-launch plan 256 x 128, tfft_plan_default_variant; a caller that names
-    # any variant bit gets exactly that variant, and 1073741824 alone changes nothing about a single-pass plan)
-    kw = {"variant": 1073741824} if tf.plan_default_variant(n, 1, batch) else {}
+    # any variant bit gets exactly that variant, and NO_LATENCY_KERNEL alone changes nothing about a single-pass plan)
+    kw = {"variant": capi.VARIANT_NO_LATENCY_KERNEL} if tf.plan_default_variant(n, 1, batch) else {}
     plan = tf.TfftPlan(n, batch, 0, **kw)
     assert plan.kernel_name == "fft4096r_kernel" and plan.num_launches == 1 and plan.workspace_bytes == 0
     gr, gi = _run(tf, torch, re, im, **kw)
@@ -380,16 +383,16 @@ def test_n4096r_single_pass_kernel(tf, torch, orc, n, batch):
 def test_radix512_column_pass(tf, torch, orc, lg, batch):
     """2^15 = 512 x 64, 2^17 = 256 x 512, 2^18 = 512 x 512, 2^23 = 256 x 512 x 64, 2^25 = 256 x 256 x 512: the radix-512 column pass (two decimated radix-256
     halves + radix-2 combine at read-out, with and without the next pass's twiddles) against the oracle, and
-    against the chain without it (variant bit 8388608), which must agree to fp16 rounding."""
+    against the chain without it (NO_RADIX512), which must agree to fp16 rounding."""
     n = 1 << lg
     rng = np.random.default_rng(lg + batch)
     re = rng.uniform(-1, 1, (batch, n)).astype(np.float16)
     im = rng.uniform(-1, 1, (batch, n)).astype(np.float16)
     # 2^13..2^15 default to the single-pass kernel: ask for the column plan; from 2^16 on name a (neutral) cache-policy bit, so that
     # the large-batch split is what runs (a variant-0 plan of a few transforms takes the small-work split, tfft_plan_default_variant)
-    multi = 16777216 if lg <= 15 else 536870912
+    multi = capi.VARIANT_COLUMN_PLAN if lg <= 15 else capi.VARIANT_COL_STREAMING
     plan = tf.TfftPlan(n, batch, 0, variant=multi)
-    no512 = multi | 8388608 | 33554432           # (without the radix-1024 pass either, which would stand in at 2^18)
+    no512 = multi | capi.VARIANT_NO_RADIX512 | capi.VARIANT_NO_RADIX1024           # (without the radix-1024 pass either, which would stand in at 2^18)
     other = tf.TfftPlan(n, batch, 0, variant=no512)
     # (2^15 without the radix-512 pass is 256 x 128 with the cooperative radix-128 pass since round 5: two launches as well)
     assert plan.num_launches == other.num_launches - (0 if lg == 15 else 1)
@@ -408,15 +411,15 @@ def test_radix1024_column_pass(tf, torch, orc, lg, batch):
     """2^19 = 512 x 1024, 2^20 = 1024 x 1024 (two passes in natural order), 2^28 = 512 x 512 x 1024: the radix-1024 column
     pass (four decimated radix-256 problems in two rounds, first-round results held in registers, radix-4 combine in two
     read-outs; both output forms, with and without the next pass's twiddles) against the oracle's fp64 DFT / N (2^28: against
-    hipFFT complex64 on the device), and against the plan without it (variant bit 33554432), to fp16 rounding."""
+    hipFFT complex64 on the device), and against the plan without it (NO_RADIX1024), to fp16 rounding."""
     n = 1 << lg
     # a few 2^19 / 2^20-point transforms default to the split with more workgroups (tfft_plan_default_variant, round 4): naming
-    # the cache-policy bit (536870912 = streaming, 262144 = plain accesses) asks for the large-batch split, the radix-1024 one
-    wide = 536870912 if lg <= 20 else 0
+    # the cache-policy bit (COL_STREAMING, COL_CACHED) asks for the large-batch split, the radix-1024 one
+    wide = capi.VARIANT_COL_STREAMING if lg <= 20 else 0
     plan = tf.TfftPlan(n, batch, 0, variant=wide)
-    other = tf.TfftPlan(n, batch, 0, variant=33554432)
+    other = tf.TfftPlan(n, batch, 0, variant=capi.VARIANT_NO_RADIX1024)
     assert plan.num_launches == other.num_launches - 1
-    assert "col:1024" in tf.plan_describe(n, 1, 0) and "col:1024" not in tf.plan_describe(n, 1, 33554432)
+    assert "col:1024" in tf.plan_describe(n, 1, 0) and "col:1024" not in tf.plan_describe(n, 1, capi.VARIANT_NO_RADIX1024)
     if lg > 24:
         gen = torch.Generator(device="cuda").manual_seed(lg)
         x = (torch.rand(batch, 2, n, device="cuda", generator=gen) * 2 - 1).half()
@@ -439,9 +442,9 @@ def test_radix1024_column_pass(tf, torch, orc, lg, batch):
     got = _c(gr, gi)
     assert np.isfinite(got).all()
     assert np.linalg.norm(got - exact) / np.linalg.norm(exact) <= REL_L2_TOL
-    qr, qi = _run(tf, torch, re, im, variant=262144)                  # the same kernels with plain accesses: the same bits
+    qr, qi = _run(tf, torch, re, im, variant=capi.VARIANT_COL_CACHED)   # the same kernels with plain accesses: the same bits
     assert np.array_equal(qr.view(np.uint16), gr.view(np.uint16)) and np.array_equal(qi.view(np.uint16), gi.view(np.uint16))
-    pr, pi = _run(tf, torch, re, im, variant=33554432)
+    pr, pi = _run(tf, torch, re, im, variant=capi.VARIANT_NO_RADIX1024)
     ref = _c(pr, pi)
     assert np.abs(got - exact).max() <= 1.5 * np.abs(ref - exact).max() + 2.0 ** -11 * np.abs(exact).max()
     # known answer: a tone at an arbitrary bin, amplitude chosen so that the line is 1.0
@@ -457,12 +460,12 @@ def test_radix1024_column_pass(tf, torch, orc, lg, batch):
 
 @pytest.mark.parametrize("lg", [13, 16, 17])
 def test_plain_autosort_chain_still_correct(tf, torch, orc, lg):
-    """variant bit 32 forces the radix-2/4/8/16 autosort chain (no radix-256 column kernel)."""
+    """AUTOSORT_ONLY forces the radix-2/4/8/16 autosort chain (no radix-256 column kernel)."""
     n = 1 << lg
     rng = np.random.default_rng(300 + lg)
     re = rng.uniform(-1, 1, (3, n)).astype(np.float16)
     im = rng.uniform(-1, 1, (3, n)).astype(np.float16)
-    gr, gi = _run(tf, torch, re, im, variant=32)
+    gr, gi = _run(tf, torch, re, im, variant=capi.VARIANT_AUTOSORT_ONLY)
     _check_against_oracle(orc, re, im, gr, gi, mode=orc.MODE_256)
 
 

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import rfft_ref
+from tensor_fft_amd import capi
 
 pytestmark = pytest.mark.gpu
 
@@ -206,13 +207,13 @@ def test_r2c_accuracy_against_float64(tf, n, scale):
 
 
 def test_fused_path_ignores_plan_wisdom(tf):
-    """A wisdom line may give a variant-0 N = 4096 complex plan another decomposition (variant 32: the plain autosort chain, no
+    """A wisdom line may give a variant-0 N = 4096 complex plan another decomposition (AUTOSORT_ONLY: the plain autosort chain, no
     N = 4096 kernel and no tables). The real plans pin their forward sub-plans to the N = 4096 kernel: the fused launch still finds
     its tables, and fused and two-pass R2C still agree bit for bit, with each other and with the result without wisdom."""
     rng = np.random.default_rng(21)
     x = _signals(rng, 5, 4096)
     plain = _r2c(tf, x)
-    tf.tuning_add(4096, 0, 32, 0)
+    tf.tuning_add(4096, 0, capi.VARIANT_AUTOSORT_ONLY, 0)
     try:
         assert tf.plan_describe(4096, 1, tf.plan_default_variant(4096, 1, 3)).startswith("autosort")
         assert tf.rplan_describe(4096, 5).startswith("r2c: k4096:4096+split | c2r: merge autosort")

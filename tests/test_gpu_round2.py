@@ -24,6 +24,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tensor_fft_amd import capi
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -243,8 +245,8 @@ def _tuner_reference(tf, torch, orc, lg):
 @pytest.mark.parametrize("lg,variant", _tuner_cases())
 def test_every_tuner_variant_against_oracle(tf, torch, orc, lg, variant):
     """tools/tuner.py's candidate lists and every (N, variant) line of the committed tuner files: each must give the
-    spectrum of the default plan within tolerance of the oracle (524288, 2097152, 1048576, 8388608 and the
-    4096-kernel masks had no parity test)."""
+    spectrum of the default plan within tolerance of the oracle (COL_WG4, NO_FUSED_TAIL, UNSTAGED_STORES,
+    NO_RADIX512 and the 4096-kernel masks had no parity test)."""
     re, im, exact, err_d = _tuner_reference(tf, torch, orc, lg)
     gr, gi = _run(tf, torch, re, im, variant=variant, preserve_input=True)
     got = _c(gr, gi)
@@ -319,9 +321,9 @@ def test_2d_fused_plan_checks_alignment(tf, torch):
 # ---------------------------------------------------------------------------------------------------------------
 # 5. scale modes (reference TensorFFT256.cu:163-177, Radix2.cu:56-65)
 # ---------------------------------------------------------------------------------------------------------------
-SCALE_CASES = [(64, 1, 0), (256, 1, 0), (1024, 1, 0), (4096, 1, 0), (8192, 1, 0), (32768, 1, 0), (8192, 1, 16777216),
-               (1 << 15, 1, 16777216), (1 << 16, 1, 0), (1 << 17, 1, 0), (1 << 18, 1, 0), (1 << 20, 1, 0), (1 << 21, 1, 0),
-               (256, 64, 0), (512, 64, 67108864), (4096, 128, 0), (1 << 16, 1, 32)]
+SCALE_CASES = [(64, 1, 0), (256, 1, 0), (1024, 1, 0), (4096, 1, 0), (8192, 1, 0), (32768, 1, 0), (8192, 1, capi.VARIANT_COLUMN_PLAN),
+               (1 << 15, 1, capi.VARIANT_COLUMN_PLAN), (1 << 16, 1, 0), (1 << 17, 1, 0), (1 << 18, 1, 0), (1 << 20, 1, 0), (1 << 21, 1, 0),
+               (256, 64, 0), (512, 64, capi.VARIANT_RADIX512_ONE_PASS), (4096, 128, 0), (1 << 16, 1, capi.VARIANT_AUTOSORT_ONLY)]
 
 
 @pytest.mark.parametrize("n,inner,variant", SCALE_CASES)
@@ -434,11 +436,13 @@ def test_transposed_order_variant_bits_and_strided_axis(tf, torch):
     re = rng.uniform(-1, 1, (2, n)).astype(np.float16)
     im = rng.uniform(-1, 1, (2, n)).astype(np.float16)
     base = _run(tf, torch, re, im, output_order="transposed")
-    for v in (16, 1, 8, 262144, 524288, 524288 | 16):
+    for v in (capi.VARIANT_K4096_PLAIN, capi.VARIANT_K4096_PREFETCH, capi.VARIANT_K4096_NONTEMPORAL, capi.VARIANT_COL_CACHED,
+              capi.VARIANT_COL_WG4, capi.VARIANT_COL_WG4 | capi.VARIANT_K4096_PLAIN):
         got = _run(tf, torch, re, im, output_order="transposed", variant=v)
         assert np.array_equal(got[0].view(np.uint16), base[0].view(np.uint16)), v
         assert np.array_equal(got[1].view(np.uint16), base[1].view(np.uint16)), v
-    for v in (32, 8388608, 33554432, 2097152, 131072):
+    for v in (capi.VARIANT_AUTOSORT_ONLY, capi.VARIANT_NO_RADIX512, capi.VARIANT_NO_RADIX1024, capi.VARIANT_NO_FUSED_TAIL,
+              capi.VARIANT_COL_PER_WAVE):
         with pytest.raises(tf.TfftError) as e:
             tf.TfftPlan(n, 2, 0, output_order="transposed", variant=v)
         assert "TRANSPOSED" in e.value.message

@@ -5,6 +5,8 @@ import sys
 import numpy as np
 import pytest
 
+from tensor_fft_amd import capi
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -98,10 +100,10 @@ def test_reference_api_uses_the_tuner_line_of_the_nearest_batch(tf, tmp_path):
 
 
 @pytest.mark.parametrize("inner,batch", [(64, 3), (128, 2), (256, 5), (4096, 2)])
-@pytest.mark.parametrize("extra", [0, 524288])
+@pytest.mark.parametrize("extra", [0, capi.VARIANT_COL_WG4])
 def test_two_round_radix512_kernel_strided_axis(tf, inner, batch, extra):
-    """colfft512r.hpp (variant bit 268435456): 128-column tiles / 8 waves where the geometry allows, 64-column tiles / 4 waves
-    otherwise or with bit 524288; against numpy's fp64 FFT and within an ulp or so of the 8-wave single-round kernel."""
+    """colfft512r.hpp (FLIP_RADIX512_KERNEL): 128-column tiles / 8 waves where the geometry allows, 64-column tiles / 4 waves
+    otherwise or with COL_WG4; against numpy's fp64 FFT and within an ulp or so of the 8-wave single-round kernel."""
     import torch
 
     n = 512
@@ -110,8 +112,9 @@ def test_two_round_radix512_kernel_strided_axis(tf, inner, batch, extra):
     im = rng.uniform(-1, 1, (batch, n, inner)).astype(np.float16)
     dev = torch.from_numpy(np.ascontiguousarray(np.stack([re, im], axis=1))).cuda().reshape(-1)
     exact = np.fft.fft(re.astype(np.float64) + 1j * im.astype(np.float64), axis=1) / n
+    one, two_round = capi.VARIANT_RADIX512_ONE_PASS, capi.VARIANT_RADIX512_ONE_PASS | capi.VARIANT_FLIP_RADIX512_KERNEL | extra
     got = {}
-    for v in (67108864, 67108864 | 268435456 | extra):
+    for v in (one, two_round):
         for scale in ("sequential", "once"):
             out = torch.full_like(dev, float("nan"))
             plan = tf.TfftPlan(n, batch, 0, inner=inner, variant=v, scale=scale)
@@ -122,11 +125,11 @@ def test_two_round_radix512_kernel_strided_axis(tf, inner, batch, extra):
             z = o[:, 0] + 1j * o[:, 1]
             assert np.linalg.norm(z - exact) / np.linalg.norm(exact) <= REL_L2_TOL, (v, scale)
             got[(v, scale)] = z
-    a, b = got[(67108864, "sequential")], got[(67108864 | 268435456 | extra, "sequential")]
+    a, b = got[(one, "sequential")], got[(two_round, "sequential")]
     assert np.abs(a - b).max() <= 2.0 ** -10 * np.abs(exact).max()       # one rounding apart, not two algorithms apart
 
 
-@pytest.mark.parametrize("variant", [268435456, 268435456 | 524288])
+@pytest.mark.parametrize("variant", [capi.VARIANT_FLIP_RADIX512_KERNEL, capi.VARIANT_FLIP_RADIX512_KERNEL | capi.VARIANT_COL_WG4])
 def test_two_round_radix512_kernel_as_last_pass_of_2pow18(tf, orc, variant):
     import torch
 

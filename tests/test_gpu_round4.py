@@ -10,6 +10,8 @@ import sys
 import numpy as np
 import pytest
 
+from tensor_fft_amd import capi
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REL_L2_TOL = 1.5e-3
@@ -269,7 +271,7 @@ def test_transposed_input_refusals(tf):
         tf.TfftPlan(1 << 20, 4, 0, input_order="transposed", scale="once")
     assert "TFFT_SCALE_ONCE" in e.value.message
     with pytest.raises(tf.TfftError):
-        tf.TfftPlan(1 << 20, 4, 0, input_order="transposed", variant=32)
+        tf.TfftPlan(1 << 20, 4, 0, input_order="transposed", variant=capi.VARIANT_AUTOSORT_ONLY)
     with pytest.raises(tf.TfftError):
         tf.TfftPlan(1 << 12, 4, 0, inner=64, input_order="transposed")
 
@@ -407,7 +409,7 @@ def test_c_abi_spectral_filter_example():
                                             (20, 16, "transposed"), (22, 4, "transposed"), (24, 1, "transposed"),
                                             (20, 16, "transposed_in")])
 def test_cache_policy_changes_the_time_never_the_result(tf, lg, batch, order):
-    """The column passes exist with plain and with non-temporal global accesses (variant bits 262144 / 536870912; neither = the
+    """The column passes exist with plain and with non-temporal global accesses (COL_CACHED / COL_STREAMING; neither = the
     library picks by the plan's footprint, tfft_plan_cache_policy): same arithmetic, so the three plans must agree to the bit."""
     import torch
 
@@ -418,7 +420,7 @@ def test_cache_policy_changes_the_time_never_the_result(tf, lg, batch, order):
     if order == "natural" and tf.plan_default_variant(n, 1, batch):
         pytest.skip("variant 0 of this shape is another split (tfft_plan_default_variant), not another cache policy of the same plan")
     outs = []
-    for v in (0, 262144, 536870912):
+    for v in (0, capi.VARIANT_COL_CACHED, capi.VARIANT_COL_STREAMING):
         plan = tf.TfftPlan(n, batch, 0, variant=v, preserve_input=True, **kw)
         ws = torch.empty(max(1, plan.workspace_bytes // 2), dtype=torch.float16, device="cuda")
         if plan.workspace_bytes:
@@ -443,7 +445,7 @@ def test_small_work_default_split_against_the_oracle_and_the_large_batch_split(t
     tf.synth_uniform(x, x[n:], n, batch)
     dv = tf.plan_default_variant(n, 1, batch)
     outs = {}
-    for name, v in (("default", 0), ("reported", dv), ("large-batch split", 536870912)):
+    for name, v in (("default", 0), ("reported", dv), ("large-batch split", capi.VARIANT_COL_STREAMING)):
         plan = tf.TfftPlan(n, batch, 0, variant=v, preserve_input=True)
         ws = torch.empty(max(1, plan.workspace_bytes // 2), dtype=torch.float16, device="cuda")
         if plan.workspace_bytes:

@@ -6,11 +6,13 @@ import os
 import numpy as np
 import pytest
 
+from tensor_fft_amd import capi
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REL_L2_TOL = 1.5e-3          # the library's stated tolerance against the fp64 DFT / N
-NO_LAT = 1073741824          # tfft_plan_opts.variant: column passes of small work by the throughput kernels
-SPLIT_256 = 8388608 | 33554432   # no radix-512 / radix-1024 passes: N = 256 x 256 x R
+NO_LAT = capi.VARIANT_NO_LATENCY_KERNEL       # column passes of small work by the throughput kernels
+SPLIT_256 = capi.VARIANT_NO_RADIX512 | capi.VARIANT_NO_RADIX1024   # N = 256 x 256 x R
 
 
 @pytest.fixture(scope="module")
@@ -52,11 +54,11 @@ def _check(orc, y, n, batch, seed, ids=None):
 def test_latency_column_kernel_against_the_oracle(tf, orc, lg, batch):
     """N = 256 x 256 x R (256 x 64 / 256 x 128 for 2^14 / 2^15) with the column passes on collat256_kernel (at most two blocks per
     CU: every batch here), both output forms, with and without the next pass's twiddles: every transform of the batch against
-    orc.dft64; and the same plan on the throughput kernels (variant bit 1073741824) agrees with it to well inside the tolerance."""
+    orc.dft64; and the same plan on the throughput kernels (NO_LATENCY_KERNEL) agrees with it to well inside the tolerance."""
     import torch
 
     n = 1 << lg
-    var = SPLIT_256 | (16777216 if lg < 16 else 0)
+    var = SPLIT_256 | (capi.VARIANT_COLUMN_PLAN if lg < 16 else 0)
     assert "col:256" in tf.plan_describe(n, 1, var)
     y = _run(tf, torch, n, batch, 50 + lg, variant=var)
     err = _check(orc, y, n, batch, 50 + lg)
@@ -272,7 +274,7 @@ def test_mfma_flops_are_linear_in_the_batch_across_the_chunk_boundary(tf, lg, or
 def test_cooperative_radix64_pass(tf, orc, lg, batch):
     """2^14 = 256 x 64 (2^13 = 256 x 32): the latency column kernel on 64 (32) columns, then stockham::tail_coop_kernel<64> (<32>)
     (4 x 4 x 4, 4 x 8 through LDS): the default for up to 4 transforms. Against orc.dft64 and against the single-pass kernel; with
-    variant bit 4194304 the final pass runs one butterfly per thread instead: same values to two roundings."""
+    PACKED the final pass runs one butterfly per thread instead: same values to two roundings."""
     import torch
 
     n = 1 << lg
@@ -280,7 +282,7 @@ def test_cooperative_radix64_pass(tf, orc, lg, batch):
     assert tf.plan_describe(n, 1, v) == "col:256+tw autosort:%d-tw" % (n // 256)
     y = _run(tf, torch, n, batch, 150 + batch)
     assert _check(orc, y, n, batch, 150 + batch) <= REL_L2_TOL
-    for other in (NO_LAT, v | 4194304):          # the single-pass kernel; the butterfly-per-thread radix-64 pass
+    for other in (NO_LAT, v | capi.VARIANT_PACKED):          # the single-pass kernel; the butterfly-per-thread radix-64 pass
         y1 = _run(tf, torch, n, batch, 150 + batch, variant=other)
         assert _check(orc, y1, n, batch, 150 + batch) <= REL_L2_TOL
         d = (y.float() - y1.float()).double()
@@ -290,12 +292,12 @@ def test_cooperative_radix64_pass(tf, orc, lg, batch):
 @pytest.mark.parametrize("n,batch", [(256, 100), (256, 3000), (1024, 40), (2048, 300), (4096, 9), (4096, 700), (8192, 300), (16384, 200)])
 def test_small_batches_spread_over_the_cus(tf, orc, n, batch):
     """A batch that does not fill the chip runs with fewer working waves per workgroup on more CUs (tfft.hip live_waves, the
-    one-group-per-workgroup form of k4096r): bit-identical to the packed launch shape (variant bit 4194304), every transform
+    one-group-per-workgroup form of k4096r): bit-identical to the packed launch shape (PACKED), every transform
     written, first / last / a middle one against the oracle."""
     import torch
 
     y = _run(tf, torch, n, batch, 170)
-    y_packed = _run(tf, torch, n, batch, 170, variant=4194304)
+    y_packed = _run(tf, torch, n, batch, 170, variant=capi.VARIANT_PACKED)
     assert bool((y.view(torch.int16) == y_packed.view(torch.int16)).all())
     assert _check(orc, y, n, batch, 170, ids=(0, batch // 2, batch - 1)) <= REL_L2_TOL
 

@@ -60,7 +60,8 @@ def _create(n=4096, batch=4, flags=0, **fields):
     (dict(inner=8), 5), (dict(inner=64), 5),
     (dict(output_order=1), 5), (dict(input_order=1), 5),
     (dict(fourstep_n=1 << 16), 5), (dict(fourstep_col0=3), 5),
-    (dict(variant=2), 5), (dict(variant=32), 5), (dict(variant=16), 5),
+    (dict(variant=capi.VARIANT_K4096_STAGE_OUT), 5), (dict(variant=capi.VARIANT_AUTOSORT_ONLY), 5),
+    (dict(variant=capi.VARIANT_K4096_PLAIN), 5),
     (dict(in_batch_stride=4088), 5), (dict(in_batch_stride=4100), 5),
     (dict(out_batch_stride=2048), 5), (dict(out_batch_stride=2052), 5), (dict(n=16, out_batch_stride=4), 5),
     (dict(preserve_input=1), 5), (dict(scale=3), 5), (dict(launch_iters=65536), 5), (dict(reserved_=1), 5),
@@ -82,11 +83,11 @@ def test_create_refuses_unknown_struct_size():
 
 
 def test_describe_keeps_the_fused_kernel_under_plan_wisdom():
-    """Wisdom for n = 4096 (variant 32 at batch 0: every batch gets the plain autosort chain) changes the complex plans, the C2R
+    """Wisdom for n = 4096 (AUTOSORT_ONLY at batch 0: every batch gets the plain autosort chain) changes the complex plans, the C2R
     chain with them, but not the forward transform of a real plan, which the fused launch and the two-pass path pin to the N = 4096
     kernel."""
     tf.tuning_clear()
-    tf.tuning_add(4096, 0, 32, 0)
+    tf.tuning_add(4096, 0, capi.VARIANT_AUTOSORT_ONLY, 0)
     try:
         assert tf.plan_describe(4096, 1, tf.plan_default_variant(4096, 1, 65536)).startswith("autosort")
         fused = tf.rplan_describe(4096, 131072)

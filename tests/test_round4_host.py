@@ -110,24 +110,25 @@ def test_small_work_gets_the_split_with_more_workgroups():
     limits on, and for every other length, it is 0; the two within-noise rules of round 4 (2^24 x 2, 2^25 x 1) live in
     profiles/r5_TunerResults.dat now (tests/test_round5_host.py)."""
     V, D = tf.plan_default_variant, tf.plan_describe
-    S = 8388608 | 33554432
+    S = capi.VARIANT_NO_RADIX512 | capi.VARIANT_NO_RADIX1024
+    F, C = capi.VARIANT_FLIP_RADIX512_KERNEL, capi.VARIANT_COLUMN_PLAN
     assert V(1 << 20, 1, 1) == S and V(1 << 20, 1, 4) == S and V(1 << 20, 1, 8) == 0 and V(1 << 20, 1, 1024) == 0
     assert D(1 << 20, 1, V(1 << 20, 1, 1)) == "col:256+tw col:256+tw autosort:16-tw" and D(1 << 20, 1, V(1 << 20, 1, 1024)) == "col:1024+tw col:1024"
     assert V(1 << 19, 1, 8) == S and V(1 << 19, 1, 16) == 0
     assert D(1 << 19, 1, V(1 << 19, 1, 1)) == "col:256+tw col:256+tw autosort:8-tw"
-    assert V(1 << 18, 1, 1) == S and V(1 << 18, 1, 4) == S and V(1 << 18, 1, 8) == 268435456 and V(1 << 18, 1, 16) == 268435456 and V(1 << 18, 1, 32) == 0
+    assert V(1 << 18, 1, 1) == S and V(1 << 18, 1, 4) == S and V(1 << 18, 1, 8) == F and V(1 << 18, 1, 16) == F and V(1 << 18, 1, 32) == 0
     assert D(1 << 18, 1, V(1 << 18, 1, 1)) == "col:256+tw col:256+tw autosort:4-tw" and D(1 << 18, 1, V(1 << 18, 1, 16)) == "col:512+tw col:512"
     assert V(1 << 21, 1, 2) == S and V(1 << 21, 1, 4) == 0
     assert D(1 << 21, 1, V(1 << 21, 1, 1)) == "col:256+tw col:256+tw autosort:32-tw"
     assert V(1 << 17, 1, 1) == S and V(1 << 17, 1, 8) == S and V(1 << 17, 1, 16) == 0 and V(1 << 17, 1, 64) == 0
     assert D(1 << 17, 1, V(1 << 17, 1, 1)) == "col:256+tw col:256+tw autosort:2-tw"
     # 2^15 up to 8 transforms: 256 x 128 (latency column kernel + the workgroup-cooperative radix-128 pass) instead of the single-pass kernel
-    assert V(1 << 15, 1, 1) == (S | 16777216) and V(1 << 15, 1, 8) == (S | 16777216) and V(1 << 15, 1, 16) == 0 and V(1 << 15, 1, 8192) == 0
+    assert V(1 << 15, 1, 1) == (S | C) and V(1 << 15, 1, 8) == (S | C) and V(1 << 15, 1, 16) == 0 and V(1 << 15, 1, 8192) == 0
     assert D(1 << 15, 1, V(1 << 15, 1, 1)) == "col:256+tw autosort:128-tw" and D(1 << 15, 1, 0) == "k4096r:8"
     # 2^14 / 2^13 up to 4 transforms: 256 x 64 / 256 x 32 the same way (cooperative radix-64 / 32 pass)
-    assert V(1 << 14, 1, 1) == (S | 16777216) and V(1 << 14, 1, 4) == (S | 16777216) and V(1 << 14, 1, 8) == 0
+    assert V(1 << 14, 1, 1) == (S | C) and V(1 << 14, 1, 4) == (S | C) and V(1 << 14, 1, 8) == 0
     assert D(1 << 14, 1, V(1 << 14, 1, 1)) == "col:256+tw autosort:64-tw"
-    assert V(1 << 13, 1, 1) == (S | 16777216) and V(1 << 13, 1, 4) == (S | 16777216) and V(1 << 13, 1, 8) == 0
+    assert V(1 << 13, 1, 1) == (S | C) and V(1 << 13, 1, 4) == (S | C) and V(1 << 13, 1, 8) == 0
     assert D(1 << 13, 1, V(1 << 13, 1, 1)) == "col:256+tw autosort:32-tw" and D(1 << 13, 1, 0) == "k4096r:2"
     for lg in (8, 12, 16, 22, 24, 25, 26):
         assert V(1 << lg, 1, 1) == 0 and V(1 << lg, 1, 2) == 0
@@ -164,6 +165,40 @@ int main(void) {
     want = [ctypes.sizeof(P), ctypes.sizeof(P), P.in_batch_stride.offset, P.fourstep_n.offset, P.launch_iters.offset,
             P.input_order.offset, ctypes.sizeof(G), ctypes.sizeof(G), G.local_passes.offset]
     assert [int(v) for v in out] == want, (out, want)
+
+
+def test_header_and_binding_agree_on_the_variant_bits(monkeypatch):
+    """The TFFT_VARIANT_* names of the header, compiled by the host compiler, equal capi's VARIANT_* in both directions;
+    tfft_variant_check takes each named bit alone for every length and axis, and refuses each of bits 0 .. 30 without a name."""
+    import re
+    import subprocess
+    import tempfile
+
+    names = re.findall(r"\b(TFFT_VARIANT_[A-Z0-9_]+) =", open(os.path.join(ROOT, "include", "tfft.h")).read())
+    src = '#include <stdio.h>\n#include "tfft.h"\nint main(void) {\n'
+    src += "".join('  printf("%s %d\\n", "{0}", (int){0});\n'.format(n) for n in names) + "  return 0;\n}\n"
+    with tempfile.TemporaryDirectory() as d:
+        c = os.path.join(d, "t.c")
+        open(c, "w").write(src)
+        exe = os.path.join(d, "t")
+        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", exe, c])
+        out = subprocess.check_output([exe], text=True).split()
+    header = {name[len("TFFT_"):]: int(v) for name, v in zip(out[::2], out[1::2])}
+    binding = {k: v for k, v in vars(capi).items() if k.startswith("VARIANT_")}
+    assert len(header) == len(names) and header == binding, set(header.items()) ^ set(binding.items())
+    bits = set(binding.values())
+    assert all(b & (b - 1) == 0 for b in bits) and len(bits) == len(binding)     # one distinct bit per name
+
+    monkeypatch.delenv("TFFT_DEBUG_VARIANTS", raising=False)
+    for lg in range(1, 31):
+        for inner in (1, 8, 64, 4096):
+            for b in bits:
+                capi.variant_check(1 << lg, inner, b)
+    for bit in range(31):
+        if (1 << bit) not in bits:
+            for n in (256, 4096, 1 << 20):
+                with pytest.raises(tf.TfftError):
+                    capi.variant_check(n, 1, 1 << bit)
 
 
 # ---- distributed setup: all ranks leave the constructor together (gloo, two ranks, an engine whose native part fails on ONE rank)

@@ -33,11 +33,12 @@ def test_a_loaded_line_changes_what_variant_zero_means(tmp_path):
                  "65536 4096 16 1 256 0 4 64\n"
                  "\n")
     assert tf.tuning_load(str(f)) == 2
-    assert tf.tuning_query(n, 2) == (33554432, 0)
+    assert tf.tuning_query(n, 2) == (capi.VARIANT_NO_RADIX1024, 0)
     after = tf.plan_describe(n, 1, tf.plan_default_variant(n, 1, 2))
     assert before == "col:512+tw col:1024+tw autosort:32-tw" and after == "col:256+tw col:256+tw col:256" and before != after
     # the line reaches three octaves either way on the batch axis, not further; other lengths are untouched
-    assert tf.tuning_query(n, 16) == (33554432, 0) and tf.tuning_query(n, 32) is None and tf.tuning_query(n, 1) == (33554432, 0)
+    no1024 = capi.VARIANT_NO_RADIX1024
+    assert tf.tuning_query(n, 16) == (no1024, 0) and tf.tuning_query(n, 32) is None and tf.tuning_query(n, 1) == (no1024, 0)
     assert tf.tuning_query(1 << 23, 2) is None and tf.tuning_query(4096, 1) is None
     # a line with variant 0 carries only its launch shape and keeps the library's default split
     assert tf.tuning_query(1 << 16, 64) == (0, 4) and tf.plan_default_variant(1 << 16, 1, 64) == 0
@@ -47,16 +48,18 @@ def test_a_loaded_line_changes_what_variant_zero_means(tmp_path):
 
 def test_nearest_batch_wins_and_later_lines_replace_earlier_ones():
     n = 1 << 18
-    tf.tuning_add(n, 1, 524288)
-    tf.tuning_add(n, 64, 268435456, 2)
+    wg4, flip, chain, no512 = (capi.VARIANT_COL_WG4, capi.VARIANT_FLIP_RADIX512_KERNEL, capi.VARIANT_AUTOSORT_ONLY,
+                               capi.VARIANT_NO_RADIX512)
+    tf.tuning_add(n, 1, wg4)
+    tf.tuning_add(n, 64, flip, 2)
     tf.tuning_add(n, 4096, 0, 8)
-    assert tf.tuning_query(n, 1) == (524288, 0) and tf.tuning_query(n, 4) == (524288, 0)
-    assert tf.tuning_query(n, 16) == (268435456, 2) and tf.tuning_query(n, 256) == (268435456, 2)
+    assert tf.tuning_query(n, 1) == (wg4, 0) and tf.tuning_query(n, 4) == (wg4, 0)
+    assert tf.tuning_query(n, 16) == (flip, 2) and tf.tuning_query(n, 256) == (flip, 2)
     assert tf.tuning_query(n, 1024) == (0, 8) and tf.tuning_query(n, 32768) == (0, 8) and tf.tuning_query(n, 65536) is None
-    tf.tuning_add(n, 64, 32)                                  # same (N, batch): replaced
-    assert tf.tuning_query(n, 64) == (32, 0)
-    tf.tuning_add(n, 0, 8388608)                              # batch 0 fits any batch, but a nearer line still wins
-    assert tf.tuning_query(n, 65536) == (8388608, 0) and tf.tuning_query(n, 64) == (32, 0)
+    tf.tuning_add(n, 64, chain)                               # same (N, batch): replaced
+    assert tf.tuning_query(n, 64) == (chain, 0)
+    tf.tuning_add(n, 0, no512)                                # batch 0 fits any batch, but a nearer line still wins
+    assert tf.tuning_query(n, 65536) == (no512, 0) and tf.tuning_query(n, 64) == (chain, 0)
 
 
 def test_bad_lines_load_nothing(tmp_path):
@@ -88,7 +91,8 @@ def test_committed_tuner_files_load_as_wisdom():
         assert tf.tuning_load(f) >= 1, f
     tf.tuning_clear()
     tf.tuning_load(os.path.join(ROOT, "profiles", "r5_TunerResults.dat"))
-    assert tf.plan_default_variant(1 << 24, 1, 2) == 33554432 and tf.plan_default_variant(1 << 25, 1, 1) == 33554432
+    no1024 = capi.VARIANT_NO_RADIX1024
+    assert tf.plan_default_variant(1 << 24, 1, 2) == no1024 and tf.plan_default_variant(1 << 25, 1, 1) == no1024
     tf.tuning_clear()
     assert tf.plan_default_variant(1 << 24, 1, 2) == 0 and tf.plan_default_variant(1 << 25, 1, 1) == 0   # no longer rules of the source
 

@@ -1,7 +1,7 @@
 """Does running a long-transform batch in cache-sized sub-batches (all passes of one sub-batch back to back) beat one
 plan over the whole batch? The 256-MiB Infinity Cache could keep a sub-batch's intermediate between passes.
 usage: [TFFT_VARIANT=262144] [ORDER=transposed | IN_ORDER=transposed] [TFFT_AB_LIB=build/libtfft_X.so] python tools/exp_chunked_batch.py N batch chunk [chunk ...]
-(262144 = no non-temporal accesses in the radix-256 column kernels)"""
+(262144 = TFFT_VARIANT_COL_CACHED: no non-temporal accesses in the radix-256 column kernels)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,6 +1,6 @@
 """Workgroup shapes of the latency column kernel (collat.hpp: columns per workgroup x waves per column group), in ONE process on
-the measurement build (TFFT_LAT_SHAPE = digits CG HH [PP]: 42 / 22 / 14 / 222 / 142, read at every launch; 0 = the throughput kernels via variant bit
-1073741824): error against numpy's fp64 FFT and device time per transform (16 executions per HIP graph).
+the measurement build (TFFT_LAT_SHAPE = digits CG HH [PP]: 42 / 22 / 14 / 222 / 142, read at every launch; 0 = the throughput kernels via
+TFFT_VARIANT_NO_LATENCY_KERNEL): error against numpy's fp64 FFT and device time per transform (16 executions per HIP graph).
     python tools/exp_lat_shapes.py [lg[:batch] ...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,9 +9,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import debuglib  # noqa: E402,F401
 import tensor_fft_amd as tf
+from tensor_fft_amd import capi
 
-SPLIT_256 = 8388608 | 33554432
-NO_LAT = 1073741824
+SPLIT_256 = capi.VARIANT_NO_RADIX512 | capi.VARIANT_NO_RADIX1024
+NO_LAT = capi.VARIANT_NO_LATENCY_KERNEL
 cases = sys.argv[1:] or ["14", "16", "17", "18", "19", "20", "21", "20:4", "18:16", "16:64"]
 for c in cases:
     f = c.split(":")
@@ -25,7 +26,7 @@ for c in cases:
     line = f"N=2^{lg} x {b}:"
     for shape in (0, 42, 22, 14, 222, 142):
         os.environ["TFFT_LAT_SHAPE"] = str(shape) if shape else "0"
-        var = SPLIT_256 | (16777216 if lg < 16 else 0) | (NO_LAT if shape == 0 else 0)
+        var = SPLIT_256 | (capi.VARIANT_COLUMN_PLAN if lg < 16 else 0) | (NO_LAT if shape == 0 else 0)
         plan = tf.TfftPlan(n, b, 0, preserve_input=True, variant=var)
         ws = torch.empty(max(1, plan.workspace_bytes // 2), dtype=torch.float16, device="cuda")
         if plan.workspace_bytes:

@@ -26,7 +26,7 @@ for n, inner, batch in ((256, 4096, 1024), (256, 1024, 4096), (256, 16384, 256))
     nf = n * inner
     x = ((torch.rand(batch * 2 * nf, device="cuda") * 2 - 1)).half()
     y = torch.empty_like(x)
-    p = tf.TfftPlan(n, batch, 0, inner=inner, variant=524288, preserve_input=True)      # 524288: 4-wave cooperative workgroups
+    p = tf.TfftPlan(n, batch, 0, inner=inner, variant=tf.capi.VARIANT_COL_WG4, preserve_input=True)      # 4-wave cooperative workgroups
     t0 = time.perf_counter()
     while time.perf_counter() - t0 < 0.2:
         p.exec(x, x[nf:], y, y[nf:])

@@ -1,5 +1,5 @@
-"""Cache policy of the column passes against the plan's footprint: streaming (non-temporal, variant bit 536870912) against
-plain accesses (variant bit 262144) and the library's own choice (variant 0), in ONE process per (N, batch), median of rounds.
+"""Cache policy of the column passes against the plan's footprint: streaming (non-temporal, TFFT_VARIANT_COL_STREAMING) against
+plain accesses (TFFT_VARIANT_COL_CACHED) and the library's own choice (variant 0), in ONE process per (N, batch), median of rounds.
 Two situations per shape: "hot" = the same buffers again and again (what a caller that iterates on one data set sees: a footprint
 below the 256-MiB Infinity Cache can stay in it), "cold" = a ring of buffer sets of > 1 GiB in total (every execution finds its
 input in HBM).
@@ -11,8 +11,9 @@ import torch
 import __graft_entry__ as g
 g.build()
 import tensor_fft_amd as tf
+from tensor_fft_amd import capi
 
-POL = (("stream", 536870912), ("plain", 262144), ("default", 0))
+POL = (("stream", capi.VARIANT_COL_STREAMING), ("plain", capi.VARIANT_COL_CACHED), ("default", 0))
 if os.environ.get("POLICIES"):        # e.g. POLICIES=stream=10,plain=2,default=0 for the N = 4096 kernel (its non-temporal bit is 8)
     POL = tuple((kv.split("=")[0], int(kv.split("=")[1])) for kv in os.environ["POLICIES"].split(","))
 KW = dict(output_order=os.environ.get("ORDER", "natural"), input_order=os.environ.get("IN_ORDER", "natural"))

@@ -10,12 +10,17 @@ import torch
 import __graft_entry__ as g
 g.build()
 import tensor_fft_amd as tf
+from tensor_fft_amd import capi
 
+SPLIT_256 = capi.VARIANT_NO_RADIX512 | capi.VARIANT_NO_RADIX1024
+VARIANTS = (0, capi.VARIANT_NO_LATENCY_KERNEL, capi.VARIANT_COL_WG4, capi.VARIANT_NO_RADIX512, capi.VARIANT_NO_RADIX1024, SPLIT_256,
+            SPLIT_256 | capi.VARIANT_NO_LATENCY_KERNEL, capi.VARIANT_FLIP_RADIX512_KERNEL,
+            capi.VARIANT_FLIP_RADIX512_KERNEL | capi.VARIANT_COL_WG4, SPLIT_256 | capi.VARIANT_COL_WG4)
 ap = argparse.ArgumentParser()
 ap.add_argument("--min-log2", type=int, default=16)
 ap.add_argument("--max-log2", type=int, default=24)
 ap.add_argument("--max-total-log2", type=int, default=25)
-ap.add_argument("--variants", default="0,1073741824,524288,8388608,33554432,41943040,1115684864,268435456,268959744,42467328")
+ap.add_argument("--variants", default=",".join(str(v) for v in VARIANTS))
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--rounds", type=int, default=5)
 args = ap.parse_args()

@@ -21,25 +21,27 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from tensor_fft_amd import capi  # noqa: E402
+
 
 def candidates(n):
-    """Kernel variants (tfft_plan_opts.variant) tried for length n. Every value here is a documented, CORRECT-result
-    variant (tests/test_gpu_round2.py runs each against the oracle); the timing-only debugging bits are not tuner input.
-    0 = library default (2|8 at N = 4096); 32 = plain autosort chain; 524288 = 4-wave cooperative column workgroups;
-    2097152 = unfused radix-16 + radix-2/4 tail; 1048576 = unstaged column stores; 16777216 = column plan instead of
-    the single-pass kernel (2^13..2^15); 8388608 = no radix-512 column passes; 33554432 = no radix-1024 column passes; 134217728 = among the
-    splits with the fewest passes, the one with the most wide (radix-1024, then radix-512) passes; 268435456 = a final radix-512
-    pass by the OTHER of its two kernels (include/tfft.h: the two-round kernel of colfft512r.hpp with 8-wave workgroups and
-    128-column tiles where the single-round kernel is the default, and vice versa; 4-wave workgroups only together with 524288);
-    262144 / 536870912 = plain / non-temporal global accesses in the column passes whatever the footprint (default: by footprint,
-    tfft_plan_cache_policy)."""
+    """Kernel variants (tfft_plan_opts.variant, the TFFT_VARIANT_* bits of include/tfft.h) tried for length n. Every value
+    here is a documented, CORRECT-result variant (tests/test_gpu_round2.py runs each against the oracle); the timing-only
+    debugging bits are not tuner input. 0 = library default (STAGE_OUT | NONTEMPORAL at N = 4096)."""
+    c = capi
     if n == 4096:
-        return [16, 2, 10, 8, 1]
+        return [c.VARIANT_K4096_PLAIN, c.VARIANT_K4096_STAGE_OUT, c.VARIANT_K4096_STAGE_OUT | c.VARIANT_K4096_NONTEMPORAL,
+                c.VARIANT_K4096_NONTEMPORAL, c.VARIANT_K4096_PREFETCH]
     if n < 8192:
-        return [0, 32]
+        return [0, c.VARIANT_AUTOSORT_ONLY]
+    split256 = c.VARIANT_NO_RADIX512 | c.VARIANT_NO_RADIX1024
     if n <= 32768:
-        return [0, 16777216, 16777216 | 8388608, 16777216 | 8388608 | 33554432, 32]     # (the last but one: 2^15 as 256 x 128, cooperative radix-128 pass)
-    return [0, 32, 524288, 2097152, 1048576, 8388608, 33554432, 8388608 | 33554432, 134217728, 268435456, 262144, 536870912]
+        return [0, c.VARIANT_COLUMN_PLAN, c.VARIANT_COLUMN_PLAN | c.VARIANT_NO_RADIX512,
+                c.VARIANT_COLUMN_PLAN | split256,        # (2^15 as 256 x 128, cooperative radix-128 pass)
+                c.VARIANT_AUTOSORT_ONLY]
+    return [0, c.VARIANT_AUTOSORT_ONLY, c.VARIANT_COL_WG4, c.VARIANT_NO_FUSED_TAIL, c.VARIANT_UNSTAGED_STORES,
+            c.VARIANT_NO_RADIX512, c.VARIANT_NO_RADIX1024, split256, c.VARIANT_WIDEST_SPLIT, c.VARIANT_FLIP_RADIX512_KERNEL,
+            c.VARIANT_COL_CACHED, c.VARIANT_COL_STREAMING]
 
 
 def iters_candidates():
