@@ -513,6 +513,17 @@ const char* tfft_plan_kernel_name(const tfft_plan* plan);
  * and the launch path can reach no instantiation outside it). Returns the number of rows, or TFFT_ERR_ARG when `bytes` is too
  * small. tests/test_isa_lint.py compares the list with the symbols of the gfx950 code object. No counterpart in the reference. */
 int tfft_kernel_list(char* buf, size_t bytes);
+/* Host only: the kernels one execution of the plan launches, one per line in launch order, named as tfft_kernel_list names them
+ * (c++filt's name of the code object's symbol without its parameter list: "k4096::fft4096_kernel<10, false, false>",
+ * "stockham::pass_kernel<16>"). A kernel launched several times is listed each time. tfft_plan_kernels: a tfft_exec out of place;
+ * tfft_plan_kernels_in_place: in place (out == in, [RE | IM] block layout) with the workspace the plan has now, which decides
+ * whether an odd chain starts with stockham::copy_kernel (tfft_plan_num_launches); tfft_rplan_kernels: tfft_exec_r2c (c2r = 0) or
+ * tfft_exec_c2r (c2r = 1). tfft_exec_inverse launches the same kernels as tfft_exec. Returns the number of lines, or TFFT_ERR_ARG
+ * when `bytes` is too small. Launches nothing, allocates nothing. */
+int tfft_plan_kernels(const tfft_plan* plan, char* buf, size_t bytes);
+int tfft_plan_kernels_in_place(const tfft_plan* plan, char* buf, size_t bytes);
+int tfft_plan2d_kernels(const tfft_plan2d* plan, char* buf, size_t bytes);
+int tfft_rplan_kernels(const tfft_rplan* plan, int c2r, char* buf, size_t bytes);
 double tfft_plan_algorithmic_bytes(const tfft_plan* plan);
 double tfft_plan_mfma_flops(const tfft_plan* plan);
 

@@ -29,6 +29,7 @@ SYMBOLS = [
     "tfft_tuning_load", "tfft_tuning_add", "tfft_tuning_clear", "tfft_tuning_query", "tfft_abi_version",
     "tfft_rplan_create", "tfft_rplan_destroy", "tfft_rplan_spectrum_pitch", "tfft_rplan_describe", "tfft_rplan_num_launches",
     "tfft_rplan_workspace_bytes", "tfft_rplan_set_workspace", "tfft_rplan_prepare", "tfft_exec_r2c", "tfft_exec_c2r",
+    "tfft_plan_kernels", "tfft_plan_kernels_in_place", "tfft_plan2d_kernels", "tfft_rplan_kernels",
 ]
 ABI_VERSION = 2                                               # TFFT_ABI_VERSION this binding's struct mirrors were written against
 
@@ -287,6 +288,11 @@ def load_library():
     L.tfft_exec_r2c.argtypes = [vp, vp, vp, vp, vp]
     L.tfft_exec_c2r.restype = ci
     L.tfft_exec_c2r.argtypes = [vp, vp, vp, vp, vp]
+    for name in ("tfft_plan_kernels", "tfft_plan_kernels_in_place", "tfft_plan2d_kernels"):
+        getattr(L, name).restype = ci
+        getattr(L, name).argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
+    L.tfft_rplan_kernels.restype = ci
+    L.tfft_rplan_kernels.argtypes = [vp, ci, ctypes.c_char_p, ctypes.c_size_t]
     L.tfft_last_error.restype = ctypes.c_char_p
     L.tfft_last_error.argtypes = []
     L.tfft_version.restype = ctypes.c_char_p
@@ -323,6 +329,21 @@ def kernel_list():
     names = buf.value.decode().split("\n")[:-1]
     assert len(names) == rc
     return names
+
+
+def _kernel_lines(fn, *args):
+    """Calls one of tfft_plan_kernels & co. with a buffer that fits: the kernels of one execution, in launch order."""
+    size = 1 << 14
+    while True:
+        buf = ctypes.create_string_buffer(size)
+        rc = fn(*args, buf, size)
+        if rc >= 0:
+            names = buf.value.decode().split("\n")[:-1]
+            assert len(names) == rc
+            return names
+        if size >= 1 << 26:
+            raise TfftError(rc, last_error())
+        size *= 4
 
 
 def tuning_load(path):
@@ -433,6 +454,16 @@ class TfftPlan:
         return self._lib.tfft_plan_kernel_name(self._h).decode()
 
     @property
+    def kernels(self):
+        """tfft_plan_kernels: the kernels one out-of-place execution launches, in launch order (demangled, without parameters)."""
+        return _kernel_lines(self._lib.tfft_plan_kernels, self._h)
+
+    @property
+    def kernels_in_place(self):
+        """tfft_plan_kernels_in_place: the same for an in-place execution with the workspace the plan has now."""
+        return _kernel_lines(self._lib.tfft_plan_kernels_in_place, self._h)
+
+    @property
     def algorithmic_bytes(self):
         return self._lib.tfft_plan_algorithmic_bytes(self._h)
 
@@ -518,6 +549,10 @@ class TfftRealPlan:
 
     def num_launches(self, c2r=False):
         return int(self._lib.tfft_rplan_num_launches(self._h, int(bool(c2r))))
+
+    def kernels(self, c2r=False):
+        """tfft_rplan_kernels: the kernels one R2C (or C2R) execution launches, in launch order."""
+        return _kernel_lines(self._lib.tfft_rplan_kernels, self._h, int(bool(c2r)))
 
     @property
     def workspace_bytes(self):
@@ -674,6 +709,11 @@ class TfftPlan2D:
     @property
     def num_launches(self):
         return int(self._lib.tfft_plan2d_num_launches(self._h))
+
+    @property
+    def kernels(self):
+        """tfft_plan2d_kernels: the kernels one execution launches, in launch order."""
+        return _kernel_lines(self._lib.tfft_plan2d_kernels, self._h)
 
     @property
     def workspace_bytes(self):

@@ -276,11 +276,32 @@ int launch_fused_r2c(const tfft_rplan* r, const void* in, void* out_re, void* ou
   k4096_shape(p, live, grid);
   const k4096::RealOut ro{r->sstride, (r->batch & 1) ? static_cast<uint32_t>(r->pairs - 1) : 0xffffffffu};
   constexpr int V = k4096::kStageOut | k4096::kNonTemporal;
-  TFFT_LAUNCH((k4096::fft4096_kernel<V, false, true>), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
+  TFFT_LAUNCH((k4096::fft4096_kernel<V, false, true>), kname("k4096::fft4096_kernel", V, false, true), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
               static_cast<const uint16_t*>(in), static_cast<const uint16_t*>(in) + r->rstride, static_cast<uint16_t*>(out_re),
               static_cast<uint16_t*>(out_im), p->in_map, p->out_map, static_cast<uint32_t>(p->batch), live,
               static_cast<const uint8_t*>(p->d_tables), p->otw, ro);
   return TFFT_OK;
+}
+
+// the split / merge pass of a real-input plan (non-temporal accesses unless the plan's cache policy says plain)
+void launch_split(const tfft_rplan* r, const rfft::SplitArgs& a, hipStream_t s) {
+  TFFT_NOTE_KERNEL(r->plain_acc ? reinterpret_cast<const void*>(rfft::split_kernel<false>) : reinterpret_cast<const void*>(rfft::split_kernel<true>),
+                   kname("rfft::split_kernel", !r->plain_acc));
+  if (g_prepare) return;
+  if (r->plain_acc)
+    hipLaunchKernelGGL(rfft::split_kernel<false>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL(rfft::split_kernel<true>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
+}
+
+void launch_merge(const tfft_rplan* r, const rfft::MergeArgs& a, hipStream_t s) {
+  TFFT_NOTE_KERNEL(r->plain_acc ? reinterpret_cast<const void*>(rfft::merge_kernel<false>) : reinterpret_cast<const void*>(rfft::merge_kernel<true>),
+                   kname("rfft::merge_kernel", !r->plain_acc));
+  if (g_prepare) return;
+  if (r->plain_acc)
+    hipLaunchKernelGGL(rfft::merge_kernel<false>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL(rfft::merge_kernel<true>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
 }
 
 void rplan_free(tfft_rplan* r) {
@@ -394,6 +415,27 @@ int tfft_rplan_describe(uint64_t n, uint64_t batch, int flags, char* buf, size_t
   return TFFT_OK;
 }
 
+int tfft_rplan_kernels(const tfft_rplan* r, int c2r, char* buf, size_t bytes) {
+  g_err.clear();
+  if (!r) return fail(TFFT_ERR_ARG, "null plan");
+  // the launch order of tfft_exec_r2c / tfft_exec_c2r; the sub-plans run out of place
+  std::vector<std::string> names;
+  int rc = TFFT_OK;
+  if (!c2r && r->fused) {
+    uint8_t* const fake = reinterpret_cast<uint8_t*>(uintptr_t{1} << 20);     // never dereferenced
+    rc = record_walk(names, [&] { return launch_fused_r2c(r, fake, fake, fake, nullptr); });
+  } else if (!c2r) {
+    for (const tfft_plan* sub : {r->fwd, r->fwd_tail})
+      if (sub && rc == TFFT_OK) rc = record_kernels(sub, false, names);
+    if (rc == TFFT_OK) rc = record_walk(names, [&] { launch_split(r, rfft::SplitArgs{}, nullptr); return TFFT_OK; });
+  } else {
+    rc = record_walk(names, [&] { launch_merge(r, rfft::MergeArgs{}, nullptr); return TFFT_OK; });
+    for (const tfft_plan* sub : {r->inv, r->inv_tail})
+      if (sub && rc == TFFT_OK) rc = record_kernels(sub, false, names);
+  }
+  return rc ? rc : put_kernel_lines(names, buf, bytes);
+}
+
 int tfft_rplan_num_launches(const tfft_rplan* r, int c2r) {
   if (!r) return 0;
   if (!c2r && r->fused) return 1;
@@ -458,10 +500,7 @@ int tfft_exec_r2c(const tfft_rplan* rc_plan, const void* in, void* out_re, void*
   }
   const rfft::SplitArgs a{z, static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), n, r->sstride,
                           static_cast<uint32_t>(r->pairs), (r->batch & 1) ? static_cast<uint32_t>(r->pairs - 1) : 0xffffffffu};
-  if (r->plain_acc)
-    hipLaunchKernelGGL(rfft::split_kernel<false>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL(rfft::split_kernel<true>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
+  launch_split(r, a, s);
   TFFT_HIP(hipGetLastError());
   return TFFT_OK;
 }
@@ -479,10 +518,7 @@ int tfft_exec_c2r(const tfft_rplan* rc_plan, const void* in_re, const void* in_i
   const uint64_t n = r->n, full = r->batch / 2;
   const rfft::MergeArgs a{static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im), z, n, r->sstride,
                           static_cast<uint32_t>(r->pairs), (r->batch & 1) ? static_cast<uint32_t>(r->pairs - 1) : 0xffffffffu};
-  if (r->plain_acc)
-    hipLaunchKernelGGL(rfft::merge_kernel<false>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL(rfft::merge_kernel<true>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
+  launch_merge(r, a, s);
   TFFT_HIP(hipGetLastError());
   uint16_t* const y = static_cast<uint16_t*>(out);
   if (r->inv) {

@@ -8,6 +8,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cxxabi.h>
+
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -111,6 +113,8 @@ int lds_opt_in(const void* fn, int device, int bytes) {
 }
 // prepare mode: walk the launch logic of a plan, run lds_opt_in for every kernel it selects, launch nothing
 thread_local bool g_prepare = false;
+// where the workspace is in prepare mode: never dereferenced, only kept apart from the (fake) data pointers of the walk
+_Float16* const kFakeWorkspace = reinterpret_cast<_Float16*>(uintptr_t{1} << 46);
 // Column slab of a four-step radix-256 pass (dist.hpp: the exchange of a distributed transform overlapped slab by slab): set around
 // a launch_chain call by tfft_dist_exec*, read by launch_col. Columns, not blocks: the block width is chosen at the launch site.
 struct SlabCtx {
@@ -120,10 +124,45 @@ struct SlabCtx {
   uint64_t out_seg_gap = 0, out_base = 0;
 };
 thread_local SlabCtx g_slab;
-#define TFFT_LAUNCH(kernel, grid, block, lds, stream, ...)                                        \
+// kernel recorder of tfft_plan_kernels & co.: set around a prepare-mode walk (which then launches and allocates nothing); every
+// launch site appends the kernel it selects, named as c++filt prints the code object's symbol without its parameter list (the names
+// of tfft_kernel_list). The name is written at the site; the recorder checks it against the runtime's symbol of the function
+// pointer launched there (hipKernelNameRefByPtr, demangled), so a name can only be listed for the kernel it names. The name
+// expression is only evaluated while recording.
+thread_local std::vector<std::string>* g_kernels = nullptr;
+thread_local std::string g_kernel_mismatch;        // first site whose name is not its function's
+inline void note_kernel(const void* fn, const std::string& name) {
+  const char* sym = hipKernelNameRefByPtr(fn, nullptr);
+  int status = -1;
+  char* dem = sym ? abi::__cxa_demangle(sym, nullptr, nullptr, &status) : nullptr;
+  std::string d = dem ? dem : (sym ? sym : "(no symbol)");
+  std::free(dem);
+  if (d.compare(0, 5, "void ") == 0) d.erase(0, 5);
+  d = d.substr(0, d.find('('));
+  if (d != name && g_kernel_mismatch.empty()) g_kernel_mismatch = name + " at the launch site of " + d;
+  g_kernels->push_back(name);
+}
+#define TFFT_NOTE_KERNEL(fn, name)                                         \
+  do {                                                                     \
+    if (g_kernels) note_kernel(reinterpret_cast<const void*>(fn), (name)); \
+  } while (0)
+inline std::string targ(bool b) { return b ? "true" : "false"; }
+inline std::string targ(int v) { return std::to_string(v); }
+template <class... A>
+std::string kname(const char* base, A... args) {
+  std::string s = std::string(base) + "<";
+  const char* sep = "";
+  ((s += sep, s += targ(args), sep = ", "), ...);
+  return s + ">";
+}
+// (lds_opt_in is a runtime call; the prepare walk at plan creation has made it for every kernel an out-of-place execution selects)
+#define TFFT_LAUNCH(kernel, name, grid, block, lds, stream, ...)                                  \
   do {                                                                                            \
-    const int rc_ = lds_opt_in(reinterpret_cast<const void*>(kernel), p->device, (lds));          \
-    if (rc_) return rc_;                                                                          \
+    TFFT_NOTE_KERNEL(kernel, name);                                                               \
+    if (!g_kernels) {                                                                             \
+      const int rc_ = lds_opt_in(reinterpret_cast<const void*>(kernel), p->device, (lds));        \
+      if (rc_) return rc_;                                                                        \
+    }                                                                                             \
     if (!g_prepare) hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);             \
   } while (0)
 
@@ -435,14 +474,14 @@ int launch_k4096_v(const tfft_plan* p, const void* in_re, const void* in_im, voi
   k4096_shape(p, live, grid);
   if constexpr (V == (k4096::kStageOut | k4096::kNonTemporal)) {
     if (p->otw.n_mask) {       // row pass of a transposed-input plan (default variant only, create_transposed_in)
-      TFFT_LAUNCH((k4096::fft4096_kernel<V, true>), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
+      TFFT_LAUNCH((k4096::fft4096_kernel<V, true>), kname("k4096::fft4096_kernel", V, true, false), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
                          static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                          static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), in_stride, out_stride,
                          static_cast<uint32_t>(p->batch), live, static_cast<const uint8_t*>(p->d_tables), p->otw, k4096::RealOut{});
       return TFFT_OK;
     }
   }
-  TFFT_LAUNCH((k4096::fft4096_kernel<V, false>), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
+  TFFT_LAUNCH((k4096::fft4096_kernel<V, false>), kname("k4096::fft4096_kernel", V, false, false), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
                      static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                      static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), in_stride, out_stride,
                      static_cast<uint32_t>(p->batch), live, static_cast<const uint8_t*>(p->d_tables), p->otw, k4096::RealOut{});
@@ -457,12 +496,12 @@ int launch_k256(const tfft_plan* p, const void* in_re, const void* in_im, void* 
   static const uint32_t iters_dflt = env_iters("TFFT_K256_ITERS", 2);
   const uint32_t grid = pick_grid(blocks_needed, p->num_cus, plan_iters(p->launch_iters, iters_dflt));
   if (p->otw.n_mask)
-    TFFT_LAUNCH(k256::fft256_kernel<true>, dim3(grid), dim3(k4096::kThreads), k256::kLdsBytes, s,
+    TFFT_LAUNCH(k256::fft256_kernel<true>, "k256::fft256_kernel<true>", dim3(grid), dim3(k4096::kThreads), k256::kLdsBytes, s,
                        static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                        static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), in_stride, out_stride,
                        static_cast<uint32_t>(p->batch), live, static_cast<const uint8_t*>(p->d_tables), p->otw);
   else
-    TFFT_LAUNCH(k256::fft256_kernel<false>, dim3(grid), dim3(k4096::kThreads), k256::kLdsBytes, s,
+    TFFT_LAUNCH(k256::fft256_kernel<false>, "k256::fft256_kernel<false>", dim3(grid), dim3(k4096::kThreads), k256::kLdsBytes, s,
                        static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                        static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), in_stride, out_stride,
                        static_cast<uint32_t>(p->batch), live, static_cast<const uint8_t*>(p->d_tables), p->otw);
@@ -479,14 +518,14 @@ int launch_k256r_t(const tfft_plan* p, const void* in_re, const void* in_im, voi
   const uint32_t grid = pick_grid(blocks_needed, p->num_cus, plan_iters(p->launch_iters, iters_dflt));
   if constexpr (STG) {
     if (p->otw.n_mask) {       // row pass of a transposed-input plan (staged stores only, create_transposed_in)
-      TFFT_LAUNCH((k256r::fft256r_kernel<R, true, true>), dim3(grid), dim3(k4096::kThreads), k256r::lds_bytes<R>(), s,
+      TFFT_LAUNCH((k256r::fft256r_kernel<R, true, true>), kname("k256r::fft256r_kernel", R, true, true), dim3(grid), dim3(k4096::kThreads), k256r::lds_bytes<R>(), s,
                          static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                          static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), in_stride, out_stride,
                          static_cast<uint32_t>(p->batch), live, static_cast<const uint8_t*>(p->d_tables), p->otw);
       return TFFT_OK;
     }
   }
-  TFFT_LAUNCH((k256r::fft256r_kernel<R, STG, false>), dim3(grid), dim3(k4096::kThreads), k256r::lds_bytes<R>(), s,
+  TFFT_LAUNCH((k256r::fft256r_kernel<R, STG, false>), kname("k256r::fft256r_kernel", R, STG, false), dim3(grid), dim3(k4096::kThreads), k256r::lds_bytes<R>(), s,
                      static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                      static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), in_stride, out_stride,
                      static_cast<uint32_t>(p->batch), live, static_cast<const uint8_t*>(p->d_tables), p->otw);
@@ -531,13 +570,16 @@ int launch_k4096r_t(const tfft_plan* p, const void* in_re, const void* in_im, vo
 #else
 #define TFFT_NO_STAMPS
 #endif
-  if (p->otw.n_mask)           // row pass of a transposed-input plan
-    TFFT_LAUNCH((k4096r::fft4096r_kernel<R, false, true>), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
+  if constexpr (R == 2) {      // (no transposed layout has N2 = 8192, tfft_plan_transposed_n2: no such instantiation either)
+    if (p->otw.n_mask) return fail(TFFT_ERR_ARG, "internal error: transposed-input row pass of 8192 points");
+  } else if (p->otw.n_mask) {  // row pass of a transposed-input plan
+    TFFT_LAUNCH((k4096r::fft4096r_kernel<R, false, true>), kname("k4096r::fft4096r_kernel", R, false, true), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
                        static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                        static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), in_stride, out_stride,
                        static_cast<uint32_t>(p->batch), per_wg, static_cast<const uint8_t*>(p->d_tables), p->otw TFFT_NO_STAMPS);
-  else
-    TFFT_LAUNCH((k4096r::fft4096r_kernel<R, false, false>), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
+    return TFFT_OK;
+  }
+  TFFT_LAUNCH((k4096r::fft4096r_kernel<R, false, false>), kname("k4096r::fft4096r_kernel", R, false, false), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
                        static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                        static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), in_stride, out_stride,
                        static_cast<uint32_t>(p->batch), per_wg, static_cast<const uint8_t*>(p->d_tables), p->otw TFFT_NO_STAMPS);
@@ -563,7 +605,7 @@ int launch_rows2d(const tfft_plan* p, const void* in_re, const void* in_im, void
   if (debug_variants_enabled())
     if (const char* e = std::getenv("TFFT_ROWS_STAMPS_PTR")) stamps = reinterpret_cast<unsigned long long*>(std::strtoull(e, nullptr, 0));
 #endif
-  TFFT_LAUNCH((k4096r::fft4096r_kernel<8, true>), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
+  TFFT_LAUNCH((k4096r::fft4096r_kernel<8, true>), "k4096r::fft4096r_kernel<8, true, false>", dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
                      static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im),
                      static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), k4096::Addr{image_stride, image_stride, 0, 0},
                      k4096::Addr{image_stride, image_stride, 0, 0}, iterations, 1u, static_cast<const uint8_t*>(p->d_tables), k4096::OutTw{}
@@ -699,8 +741,11 @@ int launch_col_row(const tfft_plan* p, uint32_t key, uint32_t grid, const colfft
   const ColRow* const r = col_row(key);
   if (!r) return fail(TFFT_ERR_ARG, "internal error: column kernel " + std::to_string(key) + " is not in the dispatch table");
   const uint32_t lds = lds_bytes ? lds_bytes : r->lds;
-  const int rc = lds_opt_in(reinterpret_cast<const void*>(r->fn), p->device, static_cast<int>(lds));
-  if (rc) return rc;
+  TFFT_NOTE_KERNEL(r->fn, r->name);
+  if (!g_kernels) {
+    const int rc = lds_opt_in(reinterpret_cast<const void*>(r->fn), p->device, static_cast<int>(lds));
+    if (rc) return rc;
+  }
   if (!g_prepare) hipLaunchKernelGGL(r->fn, dim3(grid), dim3(r->threads), lds, s, a);
   return TFFT_OK;
 }
@@ -943,6 +988,7 @@ int launch_col(const tfft_plan* p, const Pass& ps, Planes src, Planes dst, hipSt
 template <int R>
 void launch_pass(const stockham::PassArgs& a, uint64_t batch, hipStream_t s) {
   const uint64_t grid = (a.m_f * batch + stockham::kBlock - 1) / stockham::kBlock;
+  TFFT_NOTE_KERNEL(stockham::pass_kernel<R>, kname("stockham::pass_kernel", R));
   if (g_prepare) return;
   hipLaunchKernelGGL(stockham::pass_kernel<R>, dim3(static_cast<uint32_t>(grid)), dim3(stockham::kBlock), 0,
                      s, a);
@@ -951,6 +997,7 @@ void launch_pass(const stockham::PassArgs& a, uint64_t batch, hipStream_t s) {
 template <int R>
 void launch_pass_pair(const stockham::PassArgs& a, uint64_t batch, hipStream_t s) {
   const uint64_t grid = ((a.m_f / 2) * batch + stockham::kBlock - 1) / stockham::kBlock;
+  TFFT_NOTE_KERNEL(stockham::pass_pair_kernel<R>, kname("stockham::pass_pair_kernel", R));
   if (g_prepare) return;
   hipLaunchKernelGGL(stockham::pass_pair_kernel<R>, dim3(static_cast<uint32_t>(grid)), dim3(stockham::kBlock), 0,
                      s, a);
@@ -996,6 +1043,10 @@ void launch_stockham_pass(const tfft_plan* p, const Pass& ps, Planes src, Planes
       return;
     }
     const dim3 grid(static_cast<uint32_t>(a.m_f / stockham::kCoopCols * p->batch));
+    TFFT_NOTE_KERNEL(R == 128 ? reinterpret_cast<const void*>(stockham::tail_coop_kernel<128>)
+                              : R == 64 ? reinterpret_cast<const void*>(stockham::tail_coop_kernel<64>)
+                                        : reinterpret_cast<const void*>(stockham::tail_coop_kernel<32>),
+                     kname("stockham::tail_coop_kernel", R));
     if (!g_prepare) {
       if (R == 128) hipLaunchKernelGGL(stockham::tail_coop_kernel<128>, grid, dim3(256), 0, s, a);
       else if (R == 64) hipLaunchKernelGGL(stockham::tail_coop_kernel<64>, grid, dim3(128), 0, s, a);
@@ -1033,7 +1084,7 @@ int launch_chain(const tfft_plan* p, const void* in_re, const void* in_im, void*
   if (p->sub_col) {
     // TFFT_ORDER_TRANSPOSED: column pass in -> planar workspace, row pass workspace -> out (in place is fine: the input
     // has been read completely before the row pass writes)
-    _Float16* w = nullptr;
+    _Float16* w = kFakeWorkspace;
     if (!g_prepare) {
       const int rc = ensure_workspace(p);
       if (rc) return rc;
@@ -1060,7 +1111,7 @@ int launch_chain(const tfft_plan* p, const void* in_re, const void* in_im, void*
         rc = launch_chain(row, w, w_im, o_re + oo, o_im + oo, s);
       }
       if (rc) return rc;
-      if (g_prepare && !p->sub_col_tail) break;      // (prepare mode: one walk per distinct sub-plan is enough)
+      if (g_prepare && !g_kernels && !p->sub_col_tail) break;      // (LDS opt-in: one walk per distinct sub-plan is enough)
     }
     return TFFT_OK;
   }
@@ -1077,7 +1128,7 @@ int launch_chain(const tfft_plan* p, const void* in_re, const void* in_im, void*
                               : launch_k256r(p, p->passes[0].radix, in_re, in_im, out_re, out_im, p->in_map,
                                              p->out_map, s));
     if (rc) return rc;
-    TFFT_HIP(hipGetLastError());
+    if (!g_prepare) TFFT_HIP(hipGetLastError());
     return TFFT_OK;
   }
   const uint64_t nf = p->n * p->inner;
@@ -1098,7 +1149,7 @@ int launch_chain(const tfft_plan* p, const void* in_re, const void* in_im, void*
   // single-transform benchmark runs 2^18 and 2^21 in place, results_in_results_ = false, and paid 3 / 11 us for that copy).
   Planes SCR_B{};
   bool two_blocks = false;
-  if (in_place && odd && np >= 3 && !g_prepare) {
+  if (in_place && odd && np >= 3) {
     bool can;
     {
       std::lock_guard<std::mutex> lock(p->ws_mutex);
@@ -1106,10 +1157,14 @@ int launch_chain(const tfft_plan* p, const void* in_re, const void* in_im, void*
     }
     two_blocks = can;
   }
-  if (!use_in_as_scratch && (np > 1 || in_place) && !g_prepare) {
-    const int rc = ensure_workspace(p, two_blocks ? 2 : 1);
-    if (rc) return rc;
-    _Float16* w = static_cast<_Float16*>(p->ws);
+  if (!use_in_as_scratch && (np > 1 || in_place)) {
+    // (prepare mode: a workspace address of its own, so that every pass sees the pointer relations of an execution)
+    _Float16* w = kFakeWorkspace;
+    if (!g_prepare) {
+      const int rc = ensure_workspace(p, two_blocks ? 2 : 1);
+      if (rc) return rc;
+      w = static_cast<_Float16*>(p->ws);
+    }
     SCR = Planes{w, w + nf, 2 * nf};
     if (two_blocks) {
       _Float16* w2 = w + p->batch * 2 * nf;
@@ -1119,8 +1174,10 @@ int launch_chain(const tfft_plan* p, const void* in_re, const void* in_im, void*
       if (p->in_stride != 2 * nf || static_cast<const _Float16*>(in_im) != static_cast<const _Float16*>(in_re) + nf)
         return fail(TFFT_ERR_ARG, "in-place execution of this length needs the [RE|IM] block layout (batch stride 2N)");
       const uint64_t n32 = p->batch * nf;          // 4 bytes per complex sample
-      hipLaunchKernelGGL(stockham::copy_kernel, dim3(static_cast<uint32_t>(std::min<uint64_t>((n32 + 255) / 256, 8192))),
-                         dim3(stockham::kBlock), 0, s, static_cast<const uint32_t*>(in_re), static_cast<uint32_t*>(p->ws), n32);
+      TFFT_NOTE_KERNEL(stockham::copy_kernel, "stockham::copy_kernel");
+      if (!g_prepare)
+        hipLaunchKernelGGL(stockham::copy_kernel, dim3(static_cast<uint32_t>(std::min<uint64_t>((n32 + 255) / 256, 8192))),
+                           dim3(stockham::kBlock), 0, s, static_cast<const uint32_t*>(in_re), static_cast<uint32_t*>(p->ws), n32);
       SRC = SCR;
     }
   }
@@ -1150,6 +1207,40 @@ int prepare_kernels(const tfft_plan* p) {
   const int rc = launch_chain(p, fake, fake + span, fake + 2 * span, fake + 3 * span, nullptr);
   g_prepare = false;
   return rc;
+}
+
+// The kernels one execution of p launches, appended to `names` in launch order (tfft_plan_kernels): the prepare-mode walk with the
+// recorder on. Out of place over the data pointers of prepare_kernels, or in place over the [RE | IM] block layout.
+template <class Walk>
+int record_walk(std::vector<std::string>& names, Walk&& walk) {
+  g_prepare = true;
+  g_kernels = &names;
+  g_kernel_mismatch.clear();
+  const int rc = walk();
+  g_kernels = nullptr;
+  g_prepare = false;
+  if (rc == TFFT_OK && !g_kernel_mismatch.empty()) return fail(TFFT_ERR_ARG, "internal error: kernel name " + g_kernel_mismatch);
+  return rc;
+}
+
+int record_kernels(const tfft_plan* p, bool in_place, std::vector<std::string>& names) {
+  if (in_place && p->in_stride != p->out_stride) return fail(TFFT_ERR_ARG, "in-place execution needs equal input and output batch strides");
+  uint8_t* const fake = reinterpret_cast<uint8_t*>(uintptr_t{1} << 20);     // never dereferenced
+  const uint64_t span = 4 * (p->batch * std::max(p->in_stride, p->out_stride) + p->n * p->inner);
+  uint8_t* const fake_im = fake + (in_place ? 2 * p->n * p->inner : span);
+  return record_walk(names, [&] {
+    return in_place ? launch_chain(p, fake, fake_im, fake, fake_im, nullptr)
+                    : launch_chain(p, fake, fake_im, fake + 2 * span, fake + 3 * span, nullptr);
+  });
+}
+
+// names -> buf, one per line; returns how many
+int put_kernel_lines(const std::vector<std::string>& names, char* buf, size_t bytes) {
+  std::string out;
+  for (const std::string& k : names) out += k + "\n";
+  if (!buf || out.size() + 1 > bytes) return fail(TFFT_ERR_ARG, "buffer too small (" + std::to_string(out.size() + 1) + " bytes needed)");
+  std::memcpy(buf, out.c_str(), out.size() + 1);
+  return static_cast<int>(names.size());
 }
 
 // Element-exact test whether two planes (batch blocks of nf halves, `stride` halves apart) share a half.
@@ -2252,6 +2343,41 @@ int tfft_synth_uniform(void* re, void* im, uint64_t n, uint64_t batch, uint64_t 
                      static_cast<uint16_t*>(re), static_cast<uint16_t*>(im), n / 8, batch, batch_stride, first_fft, seed);
   TFFT_HIP(hipGetLastError());
   return TFFT_OK;
+}
+
+int tfft_plan_kernels(const tfft_plan* p, char* buf, size_t bytes) {
+  g_err.clear();
+  if (!p) return fail(TFFT_ERR_ARG, "null plan");
+  std::vector<std::string> names;
+  const int rc = record_kernels(p, false, names);
+  return rc ? rc : put_kernel_lines(names, buf, bytes);
+}
+
+int tfft_plan_kernels_in_place(const tfft_plan* p, char* buf, size_t bytes) {
+  g_err.clear();
+  if (!p) return fail(TFFT_ERR_ARG, "null plan");
+  std::vector<std::string> names;
+  const int rc = record_kernels(p, true, names);
+  return rc ? rc : put_kernel_lines(names, buf, bytes);
+}
+
+int tfft_plan2d_kernels(const tfft_plan2d* p, char* buf, size_t bytes) {
+  g_err.clear();
+  if (!p) return fail(TFFT_ERR_ARG, "null plan");
+  std::vector<std::string> names;
+  int rc = TFFT_OK;
+  if (p->fused) {      // per chunk of images: the fused row pass, then the column plan of that chunk (tfft_plan2d_exec)
+    uint8_t* const fake = reinterpret_cast<uint8_t*>(uintptr_t{1} << 20);     // never dereferenced
+    for (uint64_t i = 0; i < p->batch && rc == TFFT_OK; i += p->chunk) {
+      const uint64_t c = std::min<uint64_t>(p->chunk, p->batch - i);
+      rc = record_walk(names, [&] { return launch_rows2d(p->row, fake, fake, fake, fake, p->rows * p->cols, static_cast<uint32_t>(c * 512), nullptr); });
+      if (rc == TFFT_OK) rc = record_kernels(c == p->chunk ? p->col : p->col_tail, false, names);
+    }
+  } else {
+    rc = record_kernels(p->row, false, names);
+    if (rc == TFFT_OK) rc = record_kernels(p->col, false, names);
+  }
+  return rc ? rc : put_kernel_lines(names, buf, bytes);
 }
 
 int tfft_kernel_list(char* buf, size_t bytes) {

@@ -13,7 +13,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import elementwise_bound as eb
 from tensor_fft_amd import capi
+
+K_ANY = max(eb.K_TABLE, eb.K_SINCOS)        # per-element bound of a plan that may take either twiddle source
 
 pytestmark = pytest.mark.gpu
 
@@ -846,6 +849,7 @@ def test_randomized_plan_space(tf, torch):
                 assert bool((blk == keep).all()), (case, n, batch)
         rel = np.linalg.norm(got - exact) / np.linalg.norm(exact)
         assert np.isfinite(got).all() and rel <= REL_L2_TOL, (case, n, batch, planar, pad, in_place, preserve, rel)
+        eb.check(got.real, got.imag, exact.real, exact.imag, K_ANY, what=f"case {case}: N = {n} x {batch}")
 
 
 def test_randomized_strided_axis_and_2d(tf, torch):
@@ -870,6 +874,8 @@ def test_randomized_strided_axis_and_2d(tf, torch):
         exact = np.fft.fft(_c(re, im), axis=1) / n
         rel = np.linalg.norm(got - exact) / np.linalg.norm(exact)
         assert np.isfinite(got).all() and rel <= REL_L2_TOL, (case, n, inner, batch, rel)
+        g, e = got.transpose(0, 2, 1).reshape(-1, n), exact.transpose(0, 2, 1).reshape(-1, n)     # one row per transform
+        eb.check(g.real, g.imag, e.real, e.imag, K_ANY, what=f"case {case}: N = {n} inner {inner} x {batch}")
     for case in range(8):
         rows, cols = int(2 ** rng.integers(1, 11)), int(2 ** rng.integers(3, 12))
         batch = int(rng.integers(1, 4))
@@ -883,4 +889,6 @@ def test_randomized_strided_axis_and_2d(tf, torch):
         exact = np.fft.fft2(_c(re, im), axes=(1, 2)) / (rows * cols)
         rel = np.linalg.norm(got - exact) / np.linalg.norm(exact)
         assert rel <= REL_L2_TOL, (case, rows, cols, batch, rel)
+        g, e = got.reshape(batch, -1), exact.reshape(batch, -1)                                  # one row per image
+        eb.check(g.real, g.imag, e.real, e.imag, K_ANY, what=f"2D case {case}: {rows} x {cols} x {batch}")
 

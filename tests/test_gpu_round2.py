@@ -24,7 +24,10 @@ import subprocess
 import numpy as np
 import pytest
 
+import elementwise_bound as eb
 from tensor_fft_amd import capi
+
+K_ANY = max(eb.K_TABLE, eb.K_SINCOS)        # per-element bound of a plan that may take either twiddle source
 
 pytestmark = pytest.mark.gpu
 
@@ -349,6 +352,8 @@ def test_scale_modes(tf, torch, orc, n, inner, variant, scale):
     assert np.isfinite(got).all()
     rel = np.linalg.norm(got - exact) / np.linalg.norm(exact)
     assert rel <= REL_L2_TOL, (n, inner, scale, rel)
+    # every bin of every transform (one row per column of a strided axis), in ulps of that transform's own largest bin
+    eb.check(got.real, got.imag, exact.real, exact.imag, K_ANY, what=f"N = {n} inner {inner} {scale}")
 
 
 @pytest.mark.parametrize("n", [256, 4096, 8192, 1 << 16, 1 << 20])
@@ -415,6 +420,8 @@ def test_transposed_output_order(tf, torch, orc, lg, scale):
     assert np.isfinite(got).all()
     rel = np.linalg.norm(got - want) / np.linalg.norm(want)
     assert rel <= REL_L2_TOL, (lg, rel)
+    # (transposed order: the per-tile view of the check is not a column pass's tile here, only a partition of the bins)
+    eb.check(got.real, got.imag, want.real, want.imag, K_ANY, what=f"2^{lg} transposed {scale}")
     if scale == "sequential":
         # not worse than the natural-order plan on the same input, and exactly in place
         nr, ni = _run(tf, torch, re, im)

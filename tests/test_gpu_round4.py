@@ -10,7 +10,10 @@ import sys
 import numpy as np
 import pytest
 
+import elementwise_bound as eb
 from tensor_fft_amd import capi
+
+K_ANY = max(eb.K_TABLE, eb.K_SINCOS)        # per-element bound of a plan that may take either twiddle source
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -219,6 +222,7 @@ def test_transposed_input_against_the_oracle(tf, orc, lg, scale):
     for b in range(batch):
         g, ex = got[b, 0] + 1j * got[b, 1], (e_re[b] + 1j * e_im[b]) * f
         assert np.linalg.norm(g - ex) / np.linalg.norm(ex) <= REL_L2_TOL, (lg, scale, b)
+        eb.check(g.real, g.imag, ex.real, ex.imag, K_ANY, what=f"2^{lg} {scale}, transform {b}")
     # in place too (the input is consumed completely by the first pass before the second writes)
     plan2 = tf.TfftPlan(n, batch, 0, input_order="transposed", scale=scale)
     plan2.exec(x, x[n:], x, x[n:])
@@ -460,13 +464,14 @@ def test_small_work_default_split_against_the_oracle_and_the_large_batch_split(t
     if dv:
         assert np.array_equal(outs["default"].view(np.uint16), outs["reported"].view(np.uint16))
     xin = x.cpu().numpy().reshape(batch, 2, n)
-    for b in {0, batch - 1}:
+    for b in range(batch):                  # every transform of the batch
         er, ei = orc.dft64(xin[b:b + 1, 0], xin[b:b + 1, 1])                   # fp64 DFT(x) / N, the plan's scaling
         exact = er[0] + 1j * ei[0]
         for name in ("default", "large-batch split"):
             got = outs[name][b, 0].astype(np.float64) + 1j * outs[name][b, 1].astype(np.float64)
             rel = np.linalg.norm(got - exact) / np.linalg.norm(exact)
             assert rel <= 1.5e-3, (name, lg, batch, b, rel)
+            eb.check(got.real, got.imag, exact.real, exact.imag, K_ANY, what=f"{name} 2^{lg} x {batch}, transform {b}")
 
 
 @pytest.mark.parametrize("n,inner,batch", [(1 << 16, 1, 129), (1 << 16, 1, 513), (1 << 16, 1, 2049), (1 << 16, 1, 4100),

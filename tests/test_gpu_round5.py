@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import elementwise_bound as eb
 from tensor_fft_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -45,6 +46,7 @@ def _check(orc, y, n, batch, seed, ids=None):
         o = y[b * 2 * n:(b + 1) * 2 * n].cpu().numpy().astype(np.float64)
         got, exact = o[:n] + 1j * o[n:], e_re[0] + 1j * e_im[0]
         assert np.isfinite(got).all()
+        eb.check(got.real, got.imag, exact.real, exact.imag, max(eb.K_TABLE, eb.K_SINCOS), what=f"N = {n}, transform {b}")
         worst = max(worst, float(np.linalg.norm(got - exact) / np.linalg.norm(exact)))
     return worst
 
