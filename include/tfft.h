@@ -524,6 +524,11 @@ int tfft_plan_kernels(const tfft_plan* plan, char* buf, size_t bytes);
 int tfft_plan_kernels_in_place(const tfft_plan* plan, char* buf, size_t bytes);
 int tfft_plan2d_kernels(const tfft_plan2d* plan, char* buf, size_t bytes);
 int tfft_rplan_kernels(const tfft_rplan* plan, int c2r, char* buf, size_t bytes);
+/* The same for one phase of a distributed plan: phase 0 = tfft_dist_exec_pre (the column pass, once per slab), phase 1 =
+ * tfft_dist_exec_post (permute::permute_twiddle_kernel where tfft_dist_geometry.reorder is 1, then the row plan). The exchange
+ * launches no kernel of this library. Any other phase is TFFT_ERR_ARG. A TFFT_DIST_CALLER_BUFFERS plan may be asked before it
+ * has its buffers. */
+int tfft_dist_plan_kernels(const tfft_dist_plan* plan, int phase, char* buf, size_t bytes);
 double tfft_plan_algorithmic_bytes(const tfft_plan* plan);
 double tfft_plan_mfma_flops(const tfft_plan* plan);
 

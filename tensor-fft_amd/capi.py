@@ -30,6 +30,7 @@ SYMBOLS = [
     "tfft_rplan_create", "tfft_rplan_destroy", "tfft_rplan_spectrum_pitch", "tfft_rplan_describe", "tfft_rplan_num_launches",
     "tfft_rplan_workspace_bytes", "tfft_rplan_set_workspace", "tfft_rplan_prepare", "tfft_exec_r2c", "tfft_exec_c2r",
     "tfft_plan_kernels", "tfft_plan_kernels_in_place", "tfft_plan2d_kernels", "tfft_rplan_kernels",
+    "tfft_dist_plan_kernels",
 ]
 ABI_VERSION = 2                                               # TFFT_ABI_VERSION this binding's struct mirrors were written against
 
@@ -293,6 +294,8 @@ def load_library():
         getattr(L, name).argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
     L.tfft_rplan_kernels.restype = ci
     L.tfft_rplan_kernels.argtypes = [vp, ci, ctypes.c_char_p, ctypes.c_size_t]
+    L.tfft_dist_plan_kernels.restype = ci
+    L.tfft_dist_plan_kernels.argtypes = [vp, ci, ctypes.c_char_p, ctypes.c_size_t]
     L.tfft_last_error.restype = ctypes.c_char_p
     L.tfft_last_error.argtypes = []
     L.tfft_version.restype = ctypes.c_char_p
@@ -811,7 +814,7 @@ class DistPlan:
     comm: a DistComm (the RCCL exchange then runs inside exec()) or None (pre() / post() only: the caller moves the
     chunks between them, over whatever transport it has; `buffers=` hands in its own send / receive tensors)."""
 
-    def __init__(self, n, world, rank, device=0, comm=None, buffers=None, self_via_comm=False, slabs=1):
+    def __init__(self, n, world, rank, device=0, comm=None, buffers=None, self_via_comm=False, slabs=1, caller_buffers=False):
         self._lib = load_library()
         self._h = ctypes.c_void_p()
         self._comm = comm
@@ -819,7 +822,8 @@ class DistPlan:
             raise TfftError(5, "slabs must be 1, 2 or 4")
         # caller-owned exchange buffers: the plan then allocates none of its own (TFFT_DIST_CALLER_BUFFERS; 512 MiB at 2^26 on one rank)
         # slabs > 1: the exchange overlaps the column pass slab by slab inside exec() (TFFT_DIST_SLABS_*)
-        flags = ((DIST_SELF_VIA_COMM if self_via_comm else 0) | (DIST_CALLER_BUFFERS if buffers is not None else 0)
+        # caller_buffers=True without buffers=: the same flag, set_buffers() follows before the first execution
+        flags = ((DIST_SELF_VIA_COMM if self_via_comm else 0) | (DIST_CALLER_BUFFERS if buffers is not None or caller_buffers else 0)
                  | {1: 0, 2: DIST_SLABS_2, 4: DIST_SLABS_4}[slabs])
         _check(self._lib.tfft_dist_plan_create(int(n), int(world), int(rank), int(device), comm.handle if comm else None,
                                                flags, ctypes.byref(self._h)))
@@ -882,6 +886,11 @@ class DistPlan:
         with torch.cuda.device(self.device):
             _check(self._lib.tfft_dist_exec(self._h, in_re.data_ptr(), in_im.data_ptr(), out_re.data_ptr(), out_im.data_ptr(),
                                             self._stream(stream)))
+
+    def kernels(self, phase):
+        """tfft_dist_plan_kernels: the kernels pre() (phase 0, every slab) or post() (phase 1: the re-order pass, if any, then the
+        row plan) launches, in launch order."""
+        return _kernel_lines(self._lib.tfft_dist_plan_kernels, self._h, int(phase))
 
     def close(self):
         h = getattr(self, "_h", None)

@@ -100,6 +100,15 @@ int nccl_fail(ncclResult_t e, const char* what) {
     if (e_ != ncclSuccess) return nccl_fail(e_, #call);       \
   } while (0)
 
+// the row transform reads segments of `seg` samples in place when it starts with a cooperative radix-256 / radix-512 column pass
+bool rows_read_segments(uint64_t n2, uint64_t seg) {
+  std::vector<Pass> passes;
+  plan_passes(n2, 1, 0, passes);
+  const Pass& f = passes[0];
+  const uint64_t pitch = f.kind == PassKind::Col256 ? n2 / static_cast<uint64_t>(f.radix) : 0;
+  return passes.size() >= 2 && f.kind == PassKind::Col256 && (f.radix == 256 || f.radix == 512) && pitch % 128 == 0 && seg >= pitch;
+}
+
 // N1 of the split: the column pass is ONE radix-256 or radix-512 kernel with the four-step twiddle in its epilogue, and every
 // rank needs at least 64 columns (a cooperative workgroup's width). Prefer the N1 whose N2 the library transforms in the
 // fewest passes: a single-kernel length (<= 2^15, 4096 first of all); otherwise N1 = 256 (256-byte row segments).
@@ -136,14 +145,9 @@ int dist_geometry(uint64_t n, int world, int rank, tfft_dist_geometry* g) {
   g->world = world;
   g->rank = rank;
   g->fused = 1;
-  // the row transform reads segments in place when it starts with a cooperative radix-256 / radix-512 column pass
   std::vector<Pass> passes;
   plan_passes(g->n2, 1, 0, passes);
-  const Pass& f = passes[0];
-  const uint64_t pitch = f.kind == PassKind::Col256 ? g->n2 / static_cast<uint64_t>(f.radix) : 0;
-  const bool seg = world > 1 && passes.size() >= 2 && f.kind == PassKind::Col256 && (f.radix == 256 || f.radix == 512) &&
-                   pitch % 128 == 0 && g->cols >= pitch;
-  g->reorder = (world > 1 && !seg) ? 1 : 0;
+  g->reorder = (world > 1 && !rows_read_segments(g->n2, g->cols)) ? 1 : 0;
   g->local_passes = 1 + g->reorder + static_cast<int>(passes.size());
   g->slabs = 1;
   return TFFT_OK;
@@ -334,8 +338,13 @@ int tfft_dist_plan_create(uint64_t n, int world, int rank, int device_id, void* 
   if (p->slabs > 1) {
     // a slab is whole 128-column blocks of ONE four-step radix-256 column pass, and the row transforms must be able to read the
     // received pieces in place (segments of C / S samples no shorter than a row of their first column pass)
-    if (g.n1 != 256 || g.reorder || (g.cols / static_cast<uint64_t>(p->slabs)) % 128) {
-      const std::string why = g.n1 != 256 ? "its column pass is radix 512" : (g.reorder ? "its row transforms need the re-order pass" : "a slab would be narrower than 128 columns");
+    // (one rank has no re-order pass whatever its row transforms are: ask them directly)
+    const uint64_t cs = g.cols / static_cast<uint64_t>(p->slabs);
+    const bool rows_cannot = g.reorder || !rows_read_segments(g.n2, cs);
+    if (g.n1 != 256 || rows_cannot || cs % 128) {
+      const std::string why = g.n1 != 256 ? "its column pass is radix 512"
+                                          : (rows_cannot ? (g.reorder ? "its row transforms need the re-order pass" : "its row transforms cannot read the slabs' segments in place")
+                                                         : "a slab would be narrower than 128 columns");
       delete p;
       return fail(TFFT_ERR_ARG, "TFFT_DIST_SLABS_*: this geometry cannot overlap its exchange (" + why + "); create the plan without the flag");
     }
@@ -568,6 +577,34 @@ int tfft_dist_exec_post(const tfft_dist_plan* p, void* out_re, void* out_im, voi
     src_im = p->tmp_im;
   }
   return launch_chain(p->row, src_re, src_im, out_re, out_im, static_cast<hipStream_t>(stream));
+}
+
+int tfft_dist_plan_kernels(const tfft_dist_plan* p, int phase, char* buf, size_t bytes) {
+  g_err.clear();
+  if (!p) return fail(TFFT_ERR_ARG, "null plan");
+  if (phase != 0 && phase != 1) return fail(TFFT_ERR_ARG, "phase must be 0 (tfft_dist_exec_pre) or 1 (tfft_dist_exec_post)");
+  // the prepare-mode walk of the phase's own launch path with the recorder on (record_walk): the data pointers are never
+  // dereferenced, so a TFFT_DIST_CALLER_BUFFERS plan need not have its buffers yet
+  uint8_t* const fake = reinterpret_cast<uint8_t*>(uintptr_t{1} << 20);
+  const uint64_t span = 4 * (p->g.n / static_cast<uint64_t>(p->g.world));
+  std::vector<std::string> names;
+  int rc = TFFT_OK;
+  if (phase == 0) {
+    tfft_dist_plan q = *p;                 // same sub-plans and slabs, stand-in send buffers; it owns nothing
+    q.send_re = reinterpret_cast<_Float16*>(fake + 2 * span);
+    q.send_im = reinterpret_cast<_Float16*>(fake + 3 * span);
+    rc = record_walk(names, [&] {
+      int r = TFFT_OK;
+      for (int sl = 0; sl < q.slabs && r == TFFT_OK; ++sl) r = dist_launch_col(&q, sl, fake, fake + span, nullptr);
+      return r;
+    });
+  } else {
+    rc = record_walk(names, [&] {
+      if (p->g.reorder) TFFT_NOTE_KERNEL(permute::permute_twiddle_kernel, "permute::permute_twiddle_kernel");
+      return launch_chain(p->row, fake, fake + span, fake + 2 * span, fake + 3 * span, nullptr);
+    });
+  }
+  return rc ? rc : put_kernel_lines(names, buf, bytes);
 }
 
 int tfft_dist_exec(const tfft_dist_plan* p, const void* in_re, const void* in_im, void* out_re, void* out_im, void* stream) {

@@ -17,6 +17,14 @@ worst measured value of the class, at most 4):
     K_SINCOS   twiddles from hardware v_sin / v_cos (collat256_kernel, colfft256_kernel<.., .., .., false> of COL_WAVE_SINCOS)
     K_REAL     real-input plans (R2C / C2R), bounded against the largest bin of the signal PAIR that shares one complex transform
                (include/tfft.h); the scale modes none and once use the class's K relative to their own output
+
+The distributed plans (tfft_dist_*, tests/test_gpu_dist_elementwise.py) have their own profile, profiles/dist_ulps.txt
+(tools/accuracy_dist.py: per case, world and rank over three seeds), and the same rule:
+
+    K_PRE      the send buffer after tfft_dist_exec_pre (one column kernel with the four-step twiddle, one rounding), each column in
+               ulps of its own largest bin
+    K_DIST     the output after tfft_dist_exec_post with table twiddles, in ulps of the largest bin of the whole spectrum (peak=);
+               plans with a hardware sin / cos kernel among their row passes stay under K_SINCOS
 """
 import numpy as np
 
@@ -28,6 +36,13 @@ import numpy as np
 K_TABLE = 3.0
 K_SINCOS = 2.5
 K_REAL = 4.0
+# profiles/dist_ulps.txt, "class worst" lines: send buffer 1.572 ulp (2^27 over 4 ranks; 1.07 at 2^15 to 1.57 at 2^27, growing with
+# the length, not with the rank: 16 ranks of 2^26 lie between 1.24 and 1.49 without order). Output: sin / cos 0.912, at most the
+# kernel matrix's 1.64, so K_SINCOS holds; table 1.996, above the kernel matrix's 1.84, so the distributed plans get a constant
+# of their own by the same rule instead of a wider K_TABLE. The 1.996 is 2^28 over 4 ranks, checked on sampled rows in ulps of
+# THEIR largest bin, a unit that may be one binade below the whole spectrum's; every length up to 2^27 stays at or below 1.48.
+K_PRE = 2.5
+K_DIST = 3.0
 REL_L2 = 1.5e-3          # what the rel-L2-only tests assert today, now per transform and per tile
 TILE_ROWS, TILE_COLS = 256, 16     # a column pass's unit of work: 16 columns of the [256][bins / 256] view of a transform
 
@@ -44,12 +59,19 @@ def _as2d(a):
     return a.reshape(1, -1) if a.ndim == 1 else a.reshape(a.shape[0], -1)
 
 
-def errors_in_ulps(got_re, got_im, ref_re, ref_im, pairs=False):
+def errors_in_ulps(got_re, got_im, ref_re, ref_im, pairs=False, peak=None):
     """Per transform: (worst error in ulps, bin of it, |delta| in ulps of every bin). Arrays: [transforms][bins] (or one transform).
-    pairs: the unit of transforms 2p and 2p + 1 is the ulp of the larger of their largest bins (real-input plans)."""
+    pairs: the unit of transforms 2p and 2p + 1 is the ulp of the larger of their largest bins (real-input plans).
+    peak: the magnitude whose ulp is the unit, one per transform or a scalar, in place of the largest bin of each `ref` row: rows
+    that are parts of one longer transform (a rank's [K][N2] share of a distributed N-point spectrum) are judged in the ulp of
+    the largest bin of the whole, the unit the K values were measured in."""
     g_re, g_im, r_re, r_im = _as2d(got_re), _as2d(got_im), _as2d(ref_re), _as2d(ref_im)
     assert g_re.shape == r_re.shape == g_im.shape == r_im.shape, (g_re.shape, r_re.shape)
-    peak = np.sqrt(r_re * r_re + r_im * r_im).max(axis=1)
+    if peak is not None:
+        assert not pairs, "peak= and pairs= exclude each other"
+        peak = np.broadcast_to(np.asarray(peak, dtype=np.float64).reshape(-1), (g_re.shape[0],)) if np.ndim(peak) else np.full(g_re.shape[0], float(peak))
+    else:
+        peak = np.sqrt(r_re * r_re + r_im * r_im).max(axis=1)
     if pairs:
         p = peak.copy()
         for t in range(0, len(p) - 1, 2):
@@ -61,14 +83,24 @@ def errors_in_ulps(got_re, got_im, ref_re, ref_im, pairs=False):
     return d
 
 
-def check(got_re, got_im, ref_re, ref_im, k, rel_l2=REL_L2, pairs=False, what=""):
+def check(got_re, got_im, ref_re, ref_im, k, rel_l2=REL_L2, pairs=False, what="", peak=None):
     """Asserts the per-element bound and the per-transform and per-tile rel-L2 bounds; returns the worst error in ulps over all
     transforms. The tiles are 16 columns of the [256][bins / 256] view of a transform: a column pass's unit of work where the
     output is one natural-order 1D transform, only a partition of the bins for other layouts (transposed order, strided axes,
-    2D images). A tile's error energy is compared with its own energy or, if larger, the average tile's."""
-    d = errors_in_ulps(got_re, got_im, ref_re, ref_im, pairs)
+    2D images). A tile's error energy is compared with its own energy or, if larger, the average tile's. peak: see
+    errors_in_ulps; the rel-L2 bounds stay relative to each transform's (each tile's) own energy."""
+    d = errors_in_ulps(got_re, got_im, ref_re, ref_im, pairs, peak)
     g_re, g_im, r_re, r_im = _as2d(got_re), _as2d(got_im), _as2d(ref_re), _as2d(ref_im)
     worst = 0.0
+    if d.shape[0] >= 64 and d.shape[1] < TILE_ROWS * TILE_COLS * 2:
+        # many short transforms (the columns of a send buffer): all of them at once where every one passes with room to spare;
+        # anything near a bound goes through the loop below, which alone decides and words the failure
+        e_all = d.max(axis=1)
+        num = np.sqrt(((g_re - r_re) ** 2 + (g_im - r_im) ** 2).sum(axis=1))
+        den = np.sqrt((r_re ** 2 + r_im ** 2).sum(axis=1))
+        rel = np.where(den > 0, num / np.where(den > 0, den, 1.0), num)
+        if bool((e_all <= k).all()) and bool((rel <= rel_l2 * (1 - 1e-9)).all()):
+            return float(e_all.max())
     for t in range(d.shape[0]):
         k_bin = int(np.argmax(d[t]))
         e = float(d[t, k_bin])

@@ -14,6 +14,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import dist_emulate as de
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -39,39 +41,17 @@ def signal26(orc):
 
 
 def _emulate(torch, capi, xr, xi, exact, world):
-    """Runs all `world` ranks of one transform in this process; returns the worst rel-L2 error over the ranks."""
-    n = xr.size
-    plans = [capi.DistPlan(n, world, r, 0) for r in range(world)]
-    g = plans[0].geometry
-    n1, n2, c, k, chunk = int(g.n1), int(g.n2), int(g.cols), int(g.rows), int(g.chunk)
-    loc = n // world
-    mk = lambda: torch.full((loc,), float("nan"), dtype=torch.float16, device="cuda")      # noqa: E731
-    bufs = []
-    for p in plans:
-        s_re, s_im = mk(), mk()
-        b = (s_re, s_im, mk(), mk()) if world > 1 else (s_re, s_im, s_re, s_im)
-        p.set_buffers(*b)
-        bufs.append(b)
-    x2r, x2i = xr.reshape(n1, n2), xi.reshape(n1, n2)
-    for r, p in enumerate(plans):       # input layout "columns": rank r holds columns [r C, (r + 1) C) of the [N1][N2] view
-        p.pre(torch.from_numpy(np.ascontiguousarray(x2r[:, r * c:(r + 1) * c]).reshape(-1)).cuda(),
-              torch.from_numpy(np.ascontiguousarray(x2i[:, r * c:(r + 1) * c]).reshape(-1)).cuda())
-    torch.cuda.synchronize()
-    for q in range(world):              # the exchange: chunk q of rank p' -> slot p' of rank q
-        for pp in range(world):
-            if world > 1:
-                bufs[q][2][pp * chunk:(pp + 1) * chunk].copy_(bufs[pp][0][q * chunk:(q + 1) * chunk])
-                bufs[q][3][pp * chunk:(pp + 1) * chunk].copy_(bufs[pp][1][q * chunk:(q + 1) * chunk])
+    """Runs all `world` ranks of one transform in this process (tests/dist_emulate.py); returns the worst rel-L2 error over the
+    ranks. Every rank's rows are also checked element by element, in ulps of the spectrum's largest bin."""
+    res = de.run(torch, capi, xr, xi, world, keep_send=False)
+    g = res[0].g
+    peak = float(np.abs(exact).max())
+    k = de.k_of(res[0].kernels_pre + res[0].kernels_post)
     worst = 0.0
-    for r, p in enumerate(plans):
-        o_re, o_im = mk(), mk()
-        p.post(o_re, o_im)
-        torch.cuda.synchronize()
-        got = o_re.cpu().numpy().astype(np.float64) + 1j * o_im.cpu().numpy().astype(np.float64)
-        k1 = r * k + np.arange(k)[:, None]
-        want = exact[(k1 + n1 * np.arange(n2)[None, :]).reshape(-1)]          # output layout "transposed": [K][N2]
-        assert np.isfinite(got).all()
-        worst = max(worst, float(np.linalg.norm(got - want) / np.linalg.norm(want)))
+    for r in res:
+        assert not r.faults, r.faults
+        _, rel = de.check_output(r.out_re, r.out_im, de.rank_rows(exact, g, r.g.rank), peak, k, f"N = {xr.size}, rank {r.g.rank} of {world}")
+        worst = max(worst, rel)
     return worst, g
 
 
@@ -130,9 +110,12 @@ def test_rccl_communicator_with_own_chunk_through_the_collective(tf):
     sent through ncclSend / ncclRecv: the stream order kernel -> collective -> kernel of the 8-GPU path, checked at 2^20 and 2^26
     against numpy's fp64 FFT, twice (second call: same buffers, same bits)."""
     code = r'''
+import sys
 import numpy as np, torch
 import __graft_entry__ as g
 g.build()
+sys.path.insert(0, "tests")
+import elementwise_bound as eb
 from tensor_fft_amd.distributed import DistributedFFT1D, HipEngine
 for lg in (20, 26):
     n = 1 << lg
@@ -149,6 +132,9 @@ for lg in (20, 26):
     want = exact[f.output_indices()]
     rel = float(np.linalg.norm(got - want) / np.linalg.norm(want))
     assert rel < 1.5e-3, rel
+    rows = (f.n1, f.n2)                       # one rank holds X[k1 + N1 k2] as [N1][N2]: every row transform on its own
+    eb.check(got.real.reshape(rows), got.imag.reshape(rows), want.real.reshape(rows), want.imag.reshape(rows), eb.K_DIST,
+             peak=float(np.abs(exact).max()), what="N=2^%d through RCCL" % lg)
     keep = re.clone()
     re2, _ = f.forward(a, b)
     torch.cuda.synchronize()

@@ -4,6 +4,8 @@ driver's job). Needs an MI355X: `-m gpu`."""
 import numpy as np
 import pytest
 
+import elementwise_bound as eb
+
 pytestmark = pytest.mark.gpu
 
 
@@ -74,6 +76,7 @@ def test_driver_with_hip_engine_single_rank(tf, orc, lg, out_layout, fused):
     want = exact[f.output_indices()]
     rel = np.linalg.norm(got - want) / np.linalg.norm(want)
     assert rel < 1.5e-3, rel
+    eb.check(got.real, got.imag, want.real, want.imag, eb.K_DIST, peak=float(np.abs(exact).max()), what=f"2^{lg} {out_layout} fused={fused}")
     # second call reuses every buffer (nothing is allocated per step) and gives the same bits
     keep_re = re.clone()
     ptr = re.data_ptr()
@@ -99,6 +102,9 @@ def test_single_gpu_2pow26_against_oracle(tf, orc):
     got = _c(re.cpu().numpy(), im.cpu().numpy())
     rel = np.linalg.norm(got - want) / np.linalg.norm(want)
     assert rel < 1.5e-3, rel
+    rows = (f.n1, f.n2)                      # every row transform on its own, in ulps of the spectrum's largest bin
+    eb.check(got.real.reshape(rows), got.imag.reshape(rows), want.real.reshape(rows), want.imag.reshape(rows), eb.K_DIST,
+             peak=float(np.abs(want).max()), what="2^26 on one rank")
     # the library's own single-GPU plan of the same length agrees
     dev = torch.from_numpy(np.concatenate([xr[0], xi[0]])).cuda()
     out = torch.empty_like(dev)
@@ -174,6 +180,7 @@ def _rank_on_one_gpu(rank, world, port, n, in_layout, out_layout, fused, ret):
         got = _c(re.cpu().numpy(), im.cpu().numpy())
         want = exact[f.output_indices()]
         ret[rank] = float(np.linalg.norm(got - want) / np.linalg.norm(want))
+        eb.check(got.real, got.imag, want.real, want.imag, eb.K_DIST, peak=float(np.abs(exact).max()), what=f"rank {rank} of {world}")
     finally:
         dist.destroy_process_group()
 

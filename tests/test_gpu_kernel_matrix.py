@@ -16,13 +16,12 @@ import numpy as np
 import pytest
 
 import elementwise_bound as eb
+from dist_emulate import GUARD, SENTINEL, _guarded, _untouched      # guard zones: shared with the distributed plans' emulator
 from tensor_fft_amd import capi as _capi
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 4096                    # sentinel halves before and after every buffer (8 KiB)
-SENTINEL = 0x7E5A               # a binary16 NaN payload no kernel writes
 
 PREF, STAGE, NT, PLAIN = (_capi.VARIANT_K4096_PREFETCH, _capi.VARIANT_K4096_STAGE_OUT, _capi.VARIANT_K4096_NONTEMPORAL,
                           _capi.VARIANT_K4096_PLAIN)
@@ -275,21 +274,8 @@ def k_of(kernels, c):
     return {"real": eb.K_REAL, "sincos": eb.K_SINCOS, "table": eb.K_TABLE}[arithmetic_class(kernels, c)]
 
 
-def _guarded(torch, n_halves, fill=None):
-    """device buffer of GUARD + n_halves + GUARD sentinel halves, the middle optionally filled from fill (numpy float16)"""
-    host = np.full(GUARD + n_halves + GUARD, SENTINEL, dtype=np.int16)
-    if fill is not None:
-        host[GUARD:GUARD + n_halves] = np.asarray(fill, dtype=np.float16).reshape(-1).view(np.int16)
-    return torch.from_numpy(host).cuda().view(torch.float16)
-
-
 def _bits(torch, dev):
     return dev.view(torch.int16).cpu().numpy()
-
-
-def _untouched(after, before, what):
-    bad = np.nonzero(after != before)[0]
-    assert bad.size == 0, f"{what}: {bad.size} halves changed, first at {bad[:4]}"
 
 
 def _ends(a):

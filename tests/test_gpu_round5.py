@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import dist_emulate as de
 import elementwise_bound as eb
 from tensor_fft_amd import capi
 
@@ -131,40 +132,16 @@ def test_latency_kernel_many_blocks_and_strided_axis(tf, orc):
 # the exchange of a distributed transform overlapped with its column pass, slab by slab (TFFT_DIST_SLABS_*)
 # ---------------------------------------------------------------------------------------------------------------------
 def _all_ranks(torch, capi, xr, xi, world, slabs):
-    """All `world` ranks of one transform as plans in this process (comm = NULL), the exchange emulated by device copies of whole
-    chunks (a peer's chunk is one contiguous block for every number of slabs): returns every rank's output planes."""
-    n = xr.size
-    plans = [capi.DistPlan(n, world, r, 0, slabs=slabs) for r in range(world)]
-    g = plans[0].geometry
-    assert int(g.slabs) == slabs
-    n1, n2, c, chunk = int(g.n1), int(g.n2), int(g.cols), int(g.chunk)
-    loc = n // world
-    mk = lambda: torch.full((loc,), float("nan"), dtype=torch.float16, device="cuda")      # noqa: E731
-    bufs = []
-    for p in plans:
-        s_re, s_im = mk(), mk()
-        b = (s_re, s_im, mk(), mk()) if world > 1 else (s_re, s_im, s_re, s_im)
-        p.set_buffers(*b)
-        bufs.append(b)
-    x2r, x2i = xr.reshape(n1, n2), xi.reshape(n1, n2)
-    for r, p in enumerate(plans):
-        p.pre(torch.from_numpy(np.ascontiguousarray(x2r[:, r * c:(r + 1) * c]).reshape(-1)).cuda(),
-              torch.from_numpy(np.ascontiguousarray(x2i[:, r * c:(r + 1) * c]).reshape(-1)).cuda())
-    torch.cuda.synchronize()
-    if world > 1:
-        for q in range(world):
-            for pp in range(world):
-                bufs[q][2][pp * chunk:(pp + 1) * chunk].copy_(bufs[pp][0][q * chunk:(q + 1) * chunk])
-                bufs[q][3][pp * chunk:(pp + 1) * chunk].copy_(bufs[pp][1][q * chunk:(q + 1) * chunk])
-    outs = []
-    for p in plans:
-        o_re, o_im = mk(), mk()
-        p.post(o_re, o_im)
-        torch.cuda.synchronize()
-        outs.append((o_re.clone(), o_im.clone()))
-    for p in plans:
-        p.close()
-    return outs, g
+    """All `world` ranks of one transform as plans in this process (tests/dist_emulate.py: comm = NULL, the exchange emulated by
+    device copies of whole chunks, a peer's chunk being one contiguous block for every number of slabs): returns every rank's
+    output planes."""
+    res = de.run(torch, capi, xr, xi, world, slabs, keep_send=False)
+    for r in res:
+        assert not r.faults, r.faults
+    g = res[0].g
+    assert g.slabs == slabs
+    g.kernels = res[0].kernels_pre + res[0].kernels_post
+    return [(torch.from_numpy(r.out_re), torch.from_numpy(r.out_im)) for r in res], g
 
 
 @pytest.mark.parametrize("lg,world", [(25, 2), (25, 4), (26, 8), (25, 1)])
@@ -192,6 +169,8 @@ def test_column_slabs_give_the_same_bits_as_one_slab(tf, orc, lg, world):
             k1 = r * k + np.arange(k)[:, None]
             want = exact[(k1 + n1 * np.arange(n2)[None, :]).reshape(-1)]
             assert np.linalg.norm(got - want) / np.linalg.norm(want) < REL_L2_TOL
+            eb.check(got.real.reshape(k, n2), got.imag.reshape(k, n2), want.real.reshape(k, n2), want.imag.reshape(k, n2), de.k_of(g.kernels),
+                     peak=float(np.abs(exact).max()), what=f"2^{lg} over {world} ranks, rank {r}")
 
 
 def test_column_slabs_are_refused_where_the_geometry_cannot_overlap(tf):
@@ -210,9 +189,12 @@ def test_overlapped_exchange_through_a_real_communicator(tf):
     import subprocess
 
     code = r'''
+import sys
 import numpy as np, torch, time
 import __graft_entry__ as g
 g.build()
+sys.path.insert(0, "tests")
+import elementwise_bound as eb
 from tensor_fft_amd.distributed import DistributedFFT1D, HipEngine
 n = 1 << 26
 rng = np.random.default_rng(5)
@@ -237,6 +219,10 @@ for slabs in (1, 2, 4):
     want = exact[f.output_indices()]
     rel = float(np.linalg.norm(got - want) / np.linalg.norm(want))
     assert rel < 1.5e-3, rel
+    if ref is None:          # (the other S give the same bits, asserted below)
+        rows = (f.n1, f.n2)
+        eb.check(got.real.reshape(rows), got.imag.reshape(rows), want.real.reshape(rows), want.imag.reshape(rows), eb.K_DIST,
+                 peak=float(np.abs(exact).max()), what="2^26 through RCCL")
     if ref is None:
         ref = (re.clone(), im.clone())
     else:
