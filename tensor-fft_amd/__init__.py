@@ -3,12 +3,14 @@
 Import name: ``tensor_fft_amd`` (see ``tensor_fft_amd.py`` at the repository
 root; the directory carries the upstream project's hyphen).
 
-Two layers, both thin:
+Three layers, all thin:
 
 * :mod:`.capi` — ctypes binding of the C ABI ``include/tfft.h`` in
   ``libtfft.so`` (hand-written HIP, built in-tree by ``__graft_entry__.build``).
   There is NO CPU or PyTorch fallback: if the library is missing or the device is
   not gfx950, calls raise.
+* :mod:`.conv` — ctypes binding of the FFT convolution add-on ``include/tfft_conv.h`` in
+  ``libtfft_conv.so`` (layered on ``libtfft.so``; same rule: no fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -19,6 +21,8 @@ Two layers, both thin:
 from .capi import (TfftError, TfftPlan, TfftPlan2D, TfftRealPlan, device_check, irfft, rfft, rplan_cache_clear, rplan_describe, rplan_spectrum_pitch, kernel_list, lib_path, load_library, plan_cache_policy,  # noqa: F401
                    plan_default_variant, plan_describe, ref_create_plan, synth_uniform, transposed_n2, tuning_add, tuning_clear,
                    tuning_load, tuning_query, variant_check)
+from .conv import (TfftConvPlan, conv_cache_clear, conv_describe, conv_filter_slot, conv_lib_path, fftconv,  # noqa: F401
+                   load_conv_library)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -34,6 +38,7 @@ from .reference_api import (  # noqa: F401
 __all__ = [
     "TfftError", "TfftPlan", "TfftPlan2D", "TfftRealPlan", "device_check", "irfft", "rfft", "rplan_cache_clear", "rplan_describe", "rplan_spectrum_pitch", "lib_path", "load_library", "plan_cache_policy", "plan_default_variant", "plan_describe", "ref_create_plan",
     "synth_uniform", "transposed_n2", "variant_check", "kernel_list", "tuning_add", "tuning_clear", "tuning_load", "tuning_query",
+    "TfftConvPlan", "conv_cache_clear", "conv_describe", "conv_filter_slot", "conv_lib_path", "fftconv", "load_conv_library",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]
