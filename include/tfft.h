@@ -289,16 +289,29 @@ int tfft_plan_describe(uint64_t n, uint64_t inner, int variant, char* buf, size_
 /* Number of passes over the data one tfft_exec makes (= kernel launches, except that a narrow column pass with a
  * ragged batch takes two) and the bytes of device scratch it needs beyond in/out (0 for N <= 32768 with a contiguous axis). If nonzero, either hand memory in
  * with tfft_plan_set_workspace(), call tfft_plan_prepare() once, or let the first tfft_exec hipMalloc it.
- * IN PLACE (out == in) a plan with an odd number >= 3 of passes needs a third buffer: a library-owned workspace grows to twice
- * tfft_plan_workspace_bytes() at the first such call (a hipMalloc: not under stream capture), a caller's workspace of twice that
- * size is used the same way, and with a smaller caller's workspace the chain starts from a copy of the input instead (one more
- * launch, and the [RE | IM] block layout with batch stride 2 n is then required). The reference's plans say where the spectrum
- * ends up (results_in_results_, src/base/Plan.h:141-145): for 2^18 and 2^21 that is the input half, i.e. in place. */
+ * The workspace is settled once. After tfft_plan_prepare(), after tfft_plan_set_workspace(), or after any execution of the plan has
+ * returned, no tfft_exec / tfft_exec_inverse of it calls hipMalloc or hipFree, in place or out of place: executions are launches
+ * only, they can be captured into a graph, and a captured graph's workspace pointer stays valid until tfft_plan_destroy or the
+ * next tfft_plan_set_workspace. The first execution settles the workspace even where it does not use it itself (out of place with
+ * preserve_input = 0 and an odd number of passes the input is the scratch; a single strided pass needs scratch only in place): a plan
+ * that is only ever run that way, by a caller who minds the allocation, gets a block handed in, which is then never touched.
+ * IN PLACE (out == in) a plan with an odd number >= 3 of passes needs a third buffer, a second workspace block behind the first
+ * (IN -> A -> B -> ... -> IN). The block count is fixed by the plan: a workspace the LIBRARY allocates for such a plan is TWICE
+ * tfft_plan_workspace_bytes() from the start, whichever call allocates it (8 GiB instead of 4 for a single 2^30-point transform),
+ * and exactly tfft_plan_workspace_bytes() for every other plan. tfft_plan_workspace_bytes() itself stays ONE block, the least a
+ * caller must hand in. A caller's workspace of twice that size is used the same way as the library's; with a caller's single block
+ * the chain starts from a copy of the input instead (one more launch; the [RE | IM] block layout with batch stride 2 n is then
+ * required, for tfft_exec_inverse as well). All three give the bits of the out-of-place execution. A caller who minds the doubled
+ * allocation hands in a block of its own. The reference's plans say where the spectrum ends up (results_in_results_,
+ * src/base/Plan.h:141-145): for 2^18 and 2^21 that is the input half, i.e. in place. */
 int tfft_plan_num_launches(const tfft_plan* plan);
 size_t tfft_plan_workspace_bytes(const tfft_plan* plan);
 int tfft_plan_set_workspace(tfft_plan* plan, void* device_ptr, size_t bytes);
-/* Allocates the plan's own workspace NOW (no-op when it needs none or one was handed in), so that no later tfft_exec calls
- * hipMalloc: with it, execution is launches only from the first call on. */
+/* Allocates the plan's own workspace NOW (no-op when it needs none or one was handed in), at the size given above (two blocks
+ * for a plan with an odd number >= 3 of passes, else one): with it, execution is launches only from the first call on, in place
+ * or out of place. Without it the first execution allocates the same workspace, of whatever kind it is and whether it uses the
+ * workspace or not, and every later one is launches only. TFFT_ERR_WORKSPACE if a workspace was handed in that is smaller than
+ * tfft_plan_workspace_bytes(); an execution reports the same once it needs the workspace. */
 int tfft_plan_prepare(tfft_plan* plan);
 
 /* Replaces ComputeFFT(Plan&, const DataHandler&, int) and ComputeFFT(const Plan&,
@@ -518,8 +531,10 @@ int tfft_kernel_list(char* buf, size_t bytes);
  * "stockham::pass_kernel<16>"). A kernel launched several times is listed each time. tfft_plan_kernels: a tfft_exec out of place;
  * tfft_plan_kernels_in_place: in place (out == in, [RE | IM] block layout) with the workspace the plan has now, which decides
  * whether an odd chain starts with stockham::copy_kernel (tfft_plan_num_launches); tfft_rplan_kernels: tfft_exec_r2c (c2r = 0) or
- * tfft_exec_c2r (c2r = 1). tfft_exec_inverse launches the same kernels as tfft_exec. Returns the number of lines, or TFFT_ERR_ARG
- * when `bytes` is too small. Launches nothing, allocates nothing. */
+ * tfft_exec_c2r (c2r = 1). tfft_exec_inverse launches the same kernels as tfft_exec. Returns the number of lines, TFFT_ERR_ARG
+ * when `bytes` is too small, or TFFT_ERR_WORKSPACE when that execution needs the workspace and the one handed to
+ * tfft_plan_set_workspace is smaller than tfft_plan_workspace_bytes(): the error the execution itself would return. Launches
+ * nothing, allocates nothing. */
 int tfft_plan_kernels(const tfft_plan* plan, char* buf, size_t bytes);
 int tfft_plan_kernels_in_place(const tfft_plan* plan, char* buf, size_t bytes);
 int tfft_plan2d_kernels(const tfft_plan2d* plan, char* buf, size_t bytes);

@@ -479,6 +479,10 @@ class TfftPlan:
         self._ws = tensor
         _check(self._lib.tfft_plan_set_workspace(self._h, tensor.data_ptr(), tensor.numel() * tensor.element_size()))
 
+    def prepare(self):
+        """Allocates the plan's own workspace now (tfft_plan_prepare): every execution, in place or not, only launches kernels."""
+        _check(self._lib.tfft_plan_prepare(self._h))
+
     def exec_ptr(self, in_re, in_im, out_re, out_im, stream=0):
         _check(self._lib.tfft_exec(self._h, in_re, in_im, out_re, out_im, stream))
 

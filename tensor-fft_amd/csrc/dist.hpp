@@ -365,6 +365,7 @@ int tfft_dist_plan_create(uint64_t n, int world, int rank, int device_id, void* 
   co.fourstep_col0 = static_cast<uint64_t>(rank) * g.cols;
   rc = create_plan(g.n1, 1, device_id, &co, InternalOpts{}, &p->col);
   if (rc) return bail(rc);
+  p->col->out_of_place_only = true;        // input -> send buffer
   // row transforms: K contiguous rows of N2, read from the receive buffer in place (segments) or behind a re-order pass
   tfft_plan_opts ro = TFFT_PLAN_OPTS_INIT;
   ro.in_batch_stride = g.reorder || world == 1 ? g.n2 : g.cols;

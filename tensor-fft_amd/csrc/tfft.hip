@@ -240,6 +240,10 @@ struct tfft_plan {
   mutable void* ws = nullptr;
   mutable size_t ws_bytes = 0;
   mutable bool ws_owned = false;
+  // A plan that another plan owns and only ever runs out of place, always the same way (the sub-plans of a transposed-order plan,
+  // the column pass of the fused 2D plan and of a distributed plan): it acquires a workspace only in an execution that uses one.
+  // Every other plan settles its workspace in its first execution whether that one uses it or not (launch_chain).
+  bool out_of_place_only = false;
 };
 
 namespace {
@@ -1003,7 +1007,7 @@ void launch_pass_pair(const stockham::PassArgs& a, uint64_t batch, hipStream_t s
                      s, a);
 }
 
-void launch_stockham_pass(const tfft_plan* p, const Pass& ps, Planes src, Planes dst, hipStream_t s) {
+int launch_stockham_pass(const tfft_plan* p, const Pass& ps, Planes src, Planes dst, hipStream_t s) {
   stockham::PassArgs a;
   a.in_re = src.re;
   a.in_im = src.im;
@@ -1028,9 +1032,9 @@ void launch_stockham_pass(const tfft_plan* p, const Pass& ps, Planes src, Planes
   // those keep one butterfly per thread). TFFT_VARIANT_PACKED keeps the one-butterfly kernel.
   if (a.skip_tw && a.ns >= 2 && a.m_f >= 2 && R <= 8 && !(p->variant & TFFT_VARIANT_PACKED)) {
     switch (R) {
-      case 2: launch_pass_pair<2>(a, p->batch, s); return;
-      case 4: launch_pass_pair<4>(a, p->batch, s); return;
-      default: launch_pass_pair<8>(a, p->batch, s); return;
+      case 2: launch_pass_pair<2>(a, p->batch, s); return TFFT_OK;
+      case 4: launch_pass_pair<4>(a, p->batch, s); return TFFT_OK;
+      default: launch_pass_pair<8>(a, p->batch, s); return TFFT_OK;
     }
   }
   // Workgroup-cooperative final pass (stockham::tail_coop_kernel): radix 128 always (plan_passes emits it only as 2^15 = 256 x 128),
@@ -1038,10 +1042,7 @@ void launch_stockham_pass(const tfft_plan* p, const Pass& ps, Planes src, Planes
   // butterfly-per-thread kernel, whose accesses are whole lines)
   const bool coop_geom = a.skip_tw && a.ns == a.m_f && a.m_f % stockham::kCoopCols == 0 && p->inner == 1;
   if (R == 128 || ((R == 64 || R == 32) && coop_geom && p->n == 256ull * R && p->batch <= 16 && !(p->variant & TFFT_VARIANT_PACKED))) {
-    if (!coop_geom) {
-      (void)fail(TFFT_ERR_ARG, "internal error: radix-128 pass outside its geometry");
-      return;
-    }
+    if (!coop_geom) return fail(TFFT_ERR_ARG, "internal error: radix-128 pass outside its geometry");
     const dim3 grid(static_cast<uint32_t>(a.m_f / stockham::kCoopCols * p->batch));
     TFFT_NOTE_KERNEL(R == 128 ? reinterpret_cast<const void*>(stockham::tail_coop_kernel<128>)
                               : R == 64 ? reinterpret_cast<const void*>(stockham::tail_coop_kernel<64>)
@@ -1052,7 +1053,7 @@ void launch_stockham_pass(const tfft_plan* p, const Pass& ps, Planes src, Planes
       else if (R == 64) hipLaunchKernelGGL(stockham::tail_coop_kernel<64>, grid, dim3(128), 0, s, a);
       else hipLaunchKernelGGL(stockham::tail_coop_kernel<32>, grid, dim3(64), 0, s, a);
     }
-    return;
+    return TFFT_OK;
   }
   switch (R) {
     case 2: launch_pass<2>(a, p->batch, s); break;
@@ -1062,20 +1063,40 @@ void launch_stockham_pass(const tfft_plan* p, const Pass& ps, Planes src, Planes
     case 64: launch_pass<64>(a, p->batch, s); break;
     default: launch_pass<16>(a, p->batch, s); break;
   }
+  return TFFT_OK;
 }
 
-// blocks = 2: a second block behind the first (in-place execution of a plan with an odd number of passes, launch_chain); only
-// asked for when the workspace is the library's own or the caller's is large enough (workspace_blocks_available)
-int ensure_workspace(const tfft_plan* p, size_t blocks = 1) {
+// Blocks of tfft_plan_workspace_bytes() in a workspace the LIBRARY allocates: two for a chain with an odd number >= 3 of passes
+// (in place it runs IN -> A -> B -> ... -> IN, launch_chain), one for every other plan. The count follows from the plan alone, so
+// an owned workspace is allocated once, by tfft_plan_prepare or the first execution of any kind, and never grows, moves or is
+// freed by a later execution: tfft_exec stays launches only, capturable, and a captured graph keeps a valid pointer.
+inline size_t owned_workspace_blocks(const tfft_plan* p) {
+  const size_t np = p->passes.size();
+  return (np >= 3 && (np % 2) == 1) ? 2 : 1;
+}
+
+// The plan's workspace and how many blocks it holds, read under ws_mutex; allocates the library's own if there is none yet. In
+// prepare mode nothing is allocated: the address is a placeholder and the block count is what an execution would find. `needed`:
+// the calling execution uses the workspace; one that does not (it only settles it for the executions after it) takes a caller's
+// workspace that is too small as zero blocks and leaves the error to the execution that needs them.
+int acquire_workspace(const tfft_plan* p, bool needed, _Float16** w, size_t* blocks) {
   std::lock_guard<std::mutex> lock(p->ws_mutex);
-  const size_t need = tfft_plan_workspace_bytes(p) * blocks;
-  if (need == 0 || (p->ws && p->ws_bytes >= need)) return TFFT_OK;
-  if (p->ws && !p->ws_owned) return fail(TFFT_ERR_WORKSPACE, "workspace handed to tfft_plan_set_workspace is too small");
-  if (p->ws) (void)hipFree(p->ws);
-  p->ws = nullptr;
-  TFFT_HIP(hipMalloc(&p->ws, need));
-  p->ws_bytes = need;
+  const size_t block = tfft_plan_workspace_bytes(p);
+  *w = g_prepare ? kFakeWorkspace : static_cast<_Float16*>(p->ws);
+  *blocks = 0;
+  if (block == 0) return TFFT_OK;
+  if (p->ws) {
+    // (an owned workspace has owned_workspace_blocks() blocks from the start, so only a caller's can be too small)
+    if (p->ws_bytes < block) return needed ? fail(TFFT_ERR_WORKSPACE, "workspace handed to tfft_plan_set_workspace is too small") : TFFT_OK;
+    *blocks = p->ws_bytes / block;
+    return TFFT_OK;
+  }
+  *blocks = owned_workspace_blocks(p);
+  if (g_prepare) return TFFT_OK;
+  TFFT_HIP(hipMalloc(&p->ws, block * *blocks));
+  p->ws_bytes = block * *blocks;
   p->ws_owned = true;
+  *w = static_cast<_Float16*>(p->ws);
   return TFFT_OK;
 }
 
@@ -1084,12 +1105,10 @@ int launch_chain(const tfft_plan* p, const void* in_re, const void* in_im, void*
   if (p->sub_col) {
     // TFFT_ORDER_TRANSPOSED: column pass in -> planar workspace, row pass workspace -> out (in place is fine: the input
     // has been read completely before the row pass writes)
-    _Float16* w = kFakeWorkspace;
-    if (!g_prepare) {
-      const int rc = ensure_workspace(p);
-      if (rc) return rc;
-      w = static_cast<_Float16*>(p->ws);
-    }
+    _Float16* w = nullptr;
+    size_t ws_blocks = 0;
+    const int wrc = acquire_workspace(p, true, &w, &ws_blocks);
+    if (wrc) return wrc;
     _Float16* const w_im = w + p->chunk * p->n;
     const _Float16 *i_re = static_cast<const _Float16*>(in_re), *i_im = static_cast<const _Float16*>(in_im);
     _Float16 *o_re = static_cast<_Float16*>(out_re), *o_im = static_cast<_Float16*>(out_im);
@@ -1143,42 +1162,45 @@ int launch_chain(const tfft_plan* p, const void* in_re, const void* in_im, void*
   const bool use_in_as_scratch = !p->preserve_input && !in_place && odd;
   Planes SCR = IN;
   Planes SRC = IN;
-  // In place with an odd number (>= 3) of passes: the chain needs a third buffer, IN -> A -> B -> ... -> OUT (= IN). A second
-  // workspace block behind the first when the workspace is the library's own (or a caller's of twice tfft_plan_workspace_bytes);
-  // otherwise, and for a single pass, the chain starts from a copy of the input (one more launch: the reference's own
-  // single-transform benchmark runs 2^18 and 2^21 in place, results_in_results_ = false, and paid 3 / 11 us for that copy).
+  // In place with an odd number (>= 3) of passes: the chain needs a third buffer, IN -> A -> B -> ... -> OUT (= IN): the second
+  // block of the workspace. The library's own workspace of such a plan has two blocks from its allocation on
+  // (owned_workspace_blocks), and so has a caller's of twice tfft_plan_workspace_bytes. With a caller's single block, and for a
+  // single pass, the chain starts from a copy of the input instead (one more launch: the reference's own single-transform
+  // benchmark runs 2^18 and 2^21 in place, results_in_results_ = false, and paid 3 / 11 us for that copy).
+  // The workspace is settled by the first execution of any kind, also by one that does not use it (input as scratch, a single
+  // pass out of place): an in-place execution after it finds its blocks and allocates nothing (tfft.h, tfft_plan_prepare).
   Planes SCR_B{};
   bool two_blocks = false;
-  if (in_place && odd && np >= 3) {
-    bool can;
-    {
-      std::lock_guard<std::mutex> lock(p->ws_mutex);
-      can = !p->ws || p->ws_owned || p->ws_bytes >= 2 * tfft_plan_workspace_bytes(p);
-    }
-    two_blocks = can;
+  const bool needs_ws = !use_in_as_scratch && (np > 1 || in_place);
+  // (prepare mode: a workspace address of its own, so that every pass sees the pointer relations of an execution)
+  _Float16* w = nullptr;
+  size_t ws_blocks = 0;
+  if (needs_ws || !p->out_of_place_only) {
+    const int rc = acquire_workspace(p, needs_ws, &w, &ws_blocks);
+    if (rc) return rc;
   }
-  if (!use_in_as_scratch && (np > 1 || in_place)) {
-    // (prepare mode: a workspace address of its own, so that every pass sees the pointer relations of an execution)
-    _Float16* w = kFakeWorkspace;
-    if (!g_prepare) {
-      const int rc = ensure_workspace(p, two_blocks ? 2 : 1);
-      if (rc) return rc;
-      w = static_cast<_Float16*>(p->ws);
-    }
+  if (needs_ws) {
+    two_blocks = in_place && odd && np >= 3 && ws_blocks >= 2;
     SCR = Planes{w, w + nf, 2 * nf};
     if (two_blocks) {
       _Float16* w2 = w + p->batch * 2 * nf;
       SCR_B = Planes{w2, w2 + nf, 2 * nf};
     } else if (in_place && odd) {
-      // chain IN -> OUT would read and write the same block: start from a copy.
-      if (p->in_stride != 2 * nf || static_cast<const _Float16*>(in_im) != static_cast<const _Float16*>(in_re) + nf)
-        return fail(TFFT_ERR_ARG, "in-place execution of this length needs the [RE|IM] block layout (batch stride 2N)");
+      // chain IN -> OUT would read and write the same block: start from a copy of the [RE | IM] blocks. tfft_exec_inverse hands
+      // the planes in exchanged, IM in front of RE: the same blocks, copied from the lower pointer, and the chain reads the copy
+      // with the planes in the caller's order.
+      const _Float16* const re = static_cast<const _Float16*>(in_re);
+      const _Float16* const im = static_cast<const _Float16*>(in_im);
+      const bool swapped = im + nf == re;
+      if (p->in_stride != 2 * nf || !(im == re + nf || swapped))
+        return fail(TFFT_ERR_ARG, "in-place execution of this length with a workspace of one block needs the [RE | IM] block layout "
+                                  "(planes N apart, batch stride 2N)");
       const uint64_t n32 = p->batch * nf;          // 4 bytes per complex sample
       TFFT_NOTE_KERNEL(stockham::copy_kernel, "stockham::copy_kernel");
       if (!g_prepare)
         hipLaunchKernelGGL(stockham::copy_kernel, dim3(static_cast<uint32_t>(std::min<uint64_t>((n32 + 255) / 256, 8192))),
-                           dim3(stockham::kBlock), 0, s, static_cast<const uint32_t*>(in_re), static_cast<uint32_t*>(p->ws), n32);
-      SRC = SCR;
+                           dim3(stockham::kBlock), 0, s, reinterpret_cast<const uint32_t*>(swapped ? im : re), reinterpret_cast<uint32_t*>(w), n32);
+      SRC = swapped ? Planes{w + nf, w, 2 * nf} : SCR;
     }
   }
   Planes cur = SRC;
@@ -1190,7 +1212,8 @@ int launch_chain(const tfft_plan* p, const void* in_re, const void* in_im, void*
       const int rc = launch_col(p, ps, cur, dst, s);
       if (rc) return rc;
     } else {
-      launch_stockham_pass(p, ps, cur, dst, s);
+      const int rc = launch_stockham_pass(p, ps, cur, dst, s);
+      if (rc) return rc;
     }
     cur = dst;
   }
@@ -1508,6 +1531,12 @@ inline uint64_t transposed_chunk(uint64_t n, uint64_t batch, bool transposed_in)
   return std::min<uint64_t>(batch, per);
 }
 
+// (they run between the caller's blocks and the plan's chunk workspace, never in place: tfft_plan::out_of_place_only)
+inline void sub_plans_out_of_place_only(tfft_plan* p) {
+  for (tfft_plan* sub : {p->sub_col, p->sub_col_tail, p->sub_row, p->sub_row_tail})
+    if (sub) sub->out_of_place_only = true;
+}
+
 int create_transposed(tfft_plan* p, const tfft_plan_opts* opts, int device_id) {
   // N = N1 N2: column pass (n = N1 along the strided axis, N2 columns, four-step twiddle w_N^(k1 n2)) into the planar
   // workspace [RE: batch x N | IM: batch x N], then batch * N1 contiguous N2-point transforms from it into `out`, where
@@ -1550,6 +1579,7 @@ int create_transposed(tfft_plan* p, const tfft_plan_opts* opts, int device_id) {
   ri.once_log2 = ilog2(n);
   rc = create_plan(n2, p->chunk * n1, device_id, &ro, ri, &p->sub_row);
   if (rc == TFFT_OK && tail) rc = create_plan(n2, tail * n1, device_id, &ro, ri, &p->sub_row_tail);
+  if (rc == TFFT_OK) sub_plans_out_of_place_only(p);
   return rc;
 }
 
@@ -1622,6 +1652,7 @@ int create_transposed_in(tfft_plan* p, int device_id) {
   if (p->sub_col->passes.size() != 1 || p->sub_col->passes[0].kind != PassKind::Col256)
     return fail(TFFT_ERR_ARG, "transposed-order input: the column transform of this length does not plan as one pass");
   p->rows_first = true;
+  sub_plans_out_of_place_only(p);
   return TFFT_OK;
 }
 
@@ -2007,7 +2038,9 @@ int tfft_plan_prepare(tfft_plan* p) {
   int prev = 0;
   TFFT_HIP(hipGetDevice(&prev));
   TFFT_HIP(hipSetDevice(p->device));
-  const int rc = ensure_workspace(p);
+  _Float16* w = nullptr;
+  size_t ws_blocks = 0;
+  const int rc = acquire_workspace(p, true, &w, &ws_blocks);
   (void)hipSetDevice(prev);
   return rc;
 }
@@ -2129,12 +2162,14 @@ int tfft_plan2d_create(uint64_t rows, uint64_t cols, uint64_t batch, int device_
       if (rc == TFFT_OK && batch % p->chunk) {
         rc = tfft_plan_create(512, (batch % p->chunk) * 8, device_id, &co, &p->col_tail);
         if (rc == TFFT_OK) {
+          p->col_tail->out_of_place_only = true;
           p->col_tail->out_row_shift = 3;
           p->col_tail->out_sub_shift = 3;
           p->col_tail->out_sub_stride = cols;
         }
       }
       if (rc == TFFT_OK) {
+        p->col->out_of_place_only = true;      // intermediate -> out, one pass: it never uses a workspace
         p->col->out_row_shift = 3;
         p->col->out_sub_shift = 3;
         p->col->out_sub_stride = cols;
@@ -2215,15 +2250,16 @@ int tfft_plan2d_exec(const tfft_plan2d* p, const void* in_re, const void* in_im,
   g_err.clear();
   if (!p) return fail(TFFT_ERR_ARG, "null plan");
   const size_t need = tfft_plan2d_workspace_bytes(p);
+  _Float16* t_re = nullptr;
   {
     std::lock_guard<std::mutex> lock(p->ws_mutex);
-    if (!p->ws || p->ws_bytes < need) {
-      if (p->ws && !p->ws_owned) return fail(TFFT_ERR_WORKSPACE, "workspace handed to tfft_plan2d_set_workspace is too small");
+    // (the library's own workspace has `need` bytes from its allocation on: only a caller's can be too small, and no execution
+    // after the first allocates, frees or moves anything)
+    if (p->ws && p->ws_bytes < need) return fail(TFFT_ERR_WORKSPACE, "workspace handed to tfft_plan2d_set_workspace is too small");
+    if (!p->ws) {
       int prev = 0;
       TFFT_HIP(hipGetDevice(&prev));
       TFFT_HIP(hipSetDevice(p->device));
-      if (p->ws) (void)hipFree(p->ws);
-      p->ws = nullptr;
       const hipError_t e = hipMalloc(&p->ws, need);
       (void)hipSetDevice(prev);
       if (e != hipSuccess) return hip_fail(e, "hipMalloc(2D workspace)");
@@ -2240,8 +2276,8 @@ int tfft_plan2d_exec(const tfft_plan2d* p, const void* in_re, const void* in_im,
       }
       if (rc != TFFT_OK) return rc;
     }
+    t_re = static_cast<_Float16*>(p->ws);
   }
-  _Float16* t_re = static_cast<_Float16*>(p->ws);
   _Float16* t_im = t_re + static_cast<size_t>(p->fused ? p->chunk : p->batch) * p->rows * p->cols;
   if (p->fused) {
     if (!in_re || !in_im || !out_re || !out_im) return fail(TFFT_ERR_ARG, "null data pointer");

@@ -331,7 +331,8 @@ def test_cooperative_radix128_pass(tf, orc, batch):
 @pytest.mark.parametrize("lg,batch", [(18, 1), (18, 3), (21, 1), (17, 2)])
 def test_in_place_with_two_workspace_blocks(tf, orc, lg, batch):
     """In place, odd number of passes (three): with a workspace of twice tfft_plan_workspace_bytes the chain runs IN -> A -> B -> IN
-    without the leading copy; with the plain workspace it starts from a copy. Both give the out-of-place bits."""
+    without the leading copy; with the plain workspace it starts from a copy. Both give the out-of-place bits, and so does the
+    library's own workspace, which has both blocks from tfft_plan_prepare on."""
     import torch
 
     n = 1 << lg
@@ -351,3 +352,15 @@ def test_in_place_with_two_workspace_blocks(tf, orc, lg, batch):
         torch.cuda.synchronize()
         assert bool((work.view(torch.int16) == ref.view(torch.int16)).all()), blocks
     plan.close()
+    # a library-owned workspace: prepared, out of place first, then in place where it is (no copy, nothing grows)
+    own = tf.TfftPlan(n, batch, 0, preserve_input=True)
+    own.prepare()
+    assert "stockham::copy_kernel" not in own.kernels_in_place
+    out = torch.empty_like(x)
+    own.exec(x, x[n:], out, out[n:])
+    work = x.clone()
+    own.exec(work, work[n:], work, work[n:])
+    torch.cuda.synchronize()
+    assert bool((out.view(torch.int16) == ref.view(torch.int16)).all())
+    assert bool((work.view(torch.int16) == ref.view(torch.int16)).all())
+    own.close()
