@@ -237,9 +237,9 @@ int tfft_dist_comm_create(int world, int rank, const void* id128, int device_id,
   int prev = 0;
   TFFT_HIP(hipGetDevice(&prev));
   TFFT_HIP(hipSetDevice(device_id));
+  const DeviceRestore restore{prev};
   ncclComm_t c = nullptr;
   const ncclResult_t e = rccl()->CommInitRank(&c, world, id, rank);
-  (void)hipSetDevice(prev);
   if (e != ncclSuccess) return nccl_fail(e, "ncclCommInitRank");
   *comm = c;
   return TFFT_OK;
@@ -298,11 +298,11 @@ void tfft_dist_plan_destroy(tfft_dist_plan* p) {
   int prev = 0;
   (void)hipGetDevice(&prev);
   (void)hipSetDevice(p->device);
+  const DeviceRestore restore{prev};
   if (p->block) (void)hipFree(p->block);
   for (hipEvent_t e : p->slab_done) (void)hipEventDestroy(e);
   if (p->exchange_done) (void)hipEventDestroy(p->exchange_done);
   if (p->comm_stream) (void)hipStreamDestroy(p->comm_stream);
-  (void)hipSetDevice(prev);
   delete p;
 }
 
@@ -382,6 +382,7 @@ int tfft_dist_plan_create(uint64_t n, int world, int rank, int device_id, void* 
   if (p->slabs > 1) {
     int prev = 0;
     hipError_t e = hipGetDevice(&prev);
+    const DeviceRestore restore{prev};
     if (e == hipSuccess) e = hipSetDevice(device_id);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->comm_stream, hipStreamNonBlocking);
     for (int i = 0; e == hipSuccess && i < p->slabs; ++i) {
@@ -390,7 +391,6 @@ int tfft_dist_plan_create(uint64_t n, int world, int rank, int device_id, void* 
       if (e == hipSuccess) p->slab_done.push_back(ev);
     }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&p->exchange_done, hipEventDisableTiming);
-    (void)hipSetDevice(prev);
     if (e != hipSuccess) return bail(hip_fail(e, "stream / events of the overlapped exchange"));
   }
   const size_t plane = static_cast<size_t>(g.n / static_cast<uint64_t>(world)) * sizeof(_Float16);   // N / P halves
@@ -403,9 +403,9 @@ int tfft_dist_plan_create(uint64_t n, int world, int rank, int device_id, void* 
   if (total) {
     int prev = 0;
     hipError_t e = hipGetDevice(&prev);
+    const DeviceRestore restore{prev};
     if (e == hipSuccess) e = hipSetDevice(device_id);
     if (e == hipSuccess) e = hipMalloc(&p->block, total);
-    (void)hipSetDevice(prev);
     if (e != hipSuccess) return bail(hip_fail(e, "hipMalloc(distributed plan buffers)"));
     b = static_cast<uint8_t*>(p->block);
   }
@@ -493,19 +493,19 @@ int dist_check(const tfft_dist_plan* p) {
 
 namespace {
 // column pass of slab sl (all of it for S = 1) into the send buffers
-int dist_launch_col(const tfft_dist_plan* p, int sl, const void* in_re, const void* in_im, hipStream_t s) {
-  if (p->slabs == 1) return launch_chain(p->col, in_re, in_im, p->send_re, p->send_im, s);
+int dist_launch_col(const Launch& L, const tfft_dist_plan* p, int sl, const void* in_re, const void* in_im) {
+  if (p->slabs == 1) return launch_chain(L, p->col, in_re, in_im, p->send_re, p->send_im);
   const uint64_t cs = p->g.cols / static_cast<uint64_t>(p->slabs);            // columns per slab
-  g_slab.on = true;
-  g_slab.col_first = static_cast<uint64_t>(sl) * cs;
-  g_slab.col_count = cs;
-  g_slab.out_pitch_shift = static_cast<uint32_t>(ilog2(cs));                 // row k of the piece: k (C / S)
-  g_slab.out_seg_shift = static_cast<uint32_t>(ilog2(p->g.rows));            // k / K = destination rank q
-  g_slab.out_seg_gap = p->g.chunk - p->g.chunk / static_cast<uint64_t>(p->slabs);   // q K C - q K C / S
-  g_slab.out_base = static_cast<uint64_t>(sl) * (p->g.chunk / static_cast<uint64_t>(p->slabs));
-  const int rc = launch_chain(p->col, in_re, in_im, p->send_re, p->send_im, s);
-  g_slab = SlabCtx{};
-  return rc;
+  SlabCtx slab;
+  slab.col_first = static_cast<uint64_t>(sl) * cs;
+  slab.col_count = cs;
+  slab.out_pitch_shift = static_cast<uint32_t>(ilog2(cs));                 // row k of the piece: k (C / S)
+  slab.out_seg_shift = static_cast<uint32_t>(ilog2(p->g.rows));            // k / K = destination rank q
+  slab.out_seg_gap = p->g.chunk - p->g.chunk / static_cast<uint64_t>(p->slabs);   // q K C - q K C / S
+  slab.out_base = static_cast<uint64_t>(sl) * (p->g.chunk / static_cast<uint64_t>(p->slabs));
+  Launch with_slab = L;
+  with_slab.slab = &slab;
+  return launch_chain(with_slab, p->col, in_re, in_im, p->send_re, p->send_im);
 }
 
 // slab sl of chunk q (both planes) goes to rank q: one ncclGroupStart / Send + Recv per peer and plane / GroupEnd on s
@@ -547,7 +547,7 @@ int tfft_dist_exec_pre(const tfft_dist_plan* p, const void* in_re, const void* i
   if (!in_re || !in_im) return fail(TFFT_ERR_ARG, "null data pointer");
   if ((reinterpret_cast<uintptr_t>(in_re) | reinterpret_cast<uintptr_t>(in_im)) & 15) return fail(TFFT_ERR_ARG, "data pointers must be 16-byte aligned");
   for (int sl = 0; sl < p->slabs; ++sl) {
-    rc = dist_launch_col(p, sl, in_re, in_im, static_cast<hipStream_t>(stream));
+    rc = dist_launch_col(Launch::run(stream), p, sl, in_re, in_im);
     if (rc) return rc;
   }
   return TFFT_OK;
@@ -577,32 +577,32 @@ int tfft_dist_exec_post(const tfft_dist_plan* p, void* out_re, void* out_im, voi
     src_re = p->tmp_re;
     src_im = p->tmp_im;
   }
-  return launch_chain(p->row, src_re, src_im, out_re, out_im, static_cast<hipStream_t>(stream));
+  return launch_chain(Launch::run(stream), p->row, src_re, src_im, out_re, out_im);
 }
 
 int tfft_dist_plan_kernels(const tfft_dist_plan* p, int phase, char* buf, size_t bytes) {
   g_err.clear();
   if (!p) return fail(TFFT_ERR_ARG, "null plan");
   if (phase != 0 && phase != 1) return fail(TFFT_ERR_ARG, "phase must be 0 (tfft_dist_exec_pre) or 1 (tfft_dist_exec_post)");
-  // the prepare-mode walk of the phase's own launch path with the recorder on (record_walk): the data pointers are never
-  // dereferenced, so a TFFT_DIST_CALLER_BUFFERS plan need not have its buffers yet
-  uint8_t* const fake = reinterpret_cast<uint8_t*>(uintptr_t{1} << 20);
-  const uint64_t span = 4 * (p->g.n / static_cast<uint64_t>(p->g.world));
+  // the Record walk of the phase's own launch path (record_walk): the data pointers are stand-ins, so a TFFT_DIST_CALLER_BUFFERS plan
+  // need not have its buffers yet
+  const WalkPtrs f = walk_ptrs(4 * (p->g.n / static_cast<uint64_t>(p->g.world)));
   std::vector<std::string> names;
   int rc = TFFT_OK;
   if (phase == 0) {
     tfft_dist_plan q = *p;                 // same sub-plans and slabs, stand-in send buffers; it owns nothing
-    q.send_re = reinterpret_cast<_Float16*>(fake + 2 * span);
-    q.send_im = reinterpret_cast<_Float16*>(fake + 3 * span);
-    rc = record_walk(names, [&] {
+    q.send_re = reinterpret_cast<_Float16*>(f.out_re);
+    q.send_im = reinterpret_cast<_Float16*>(f.out_im);
+    rc = record_walk(names, [&](const Launch& L) {
       int r = TFFT_OK;
-      for (int sl = 0; sl < q.slabs && r == TFFT_OK; ++sl) r = dist_launch_col(&q, sl, fake, fake + span, nullptr);
+      for (int sl = 0; sl < q.slabs && r == TFFT_OK; ++sl) r = dist_launch_col(L, &q, sl, f.in_re, f.in_im);
       return r;
     });
   } else {
-    rc = record_walk(names, [&] {
-      if (p->g.reorder) TFFT_NOTE_KERNEL(permute::permute_twiddle_kernel, "permute::permute_twiddle_kernel");
-      return launch_chain(p->row, fake, fake + span, fake + 2 * span, fake + 3 * span, nullptr);
+    rc = record_walk(names, [&](const Launch& L) {
+      // (tfft_dist_exec_post launches it through tfft_permute_twiddle, outside the launch layer: a note only)
+      if (p->g.reorder) (void)launch(L, p->device, permute::permute_twiddle_kernel, kname("permute::permute_twiddle_kernel"), dim3(), dim3(), 0, permute::Args{});
+      return launch_chain(L, p->row, f.in_re, f.in_im, f.out_re, f.out_im);
     });
   }
   return rc ? rc : put_kernel_lines(names, buf, bytes);
@@ -621,7 +621,7 @@ int tfft_dist_exec(const tfft_dist_plan* p, const void* in_re, const void* in_im
     if ((reinterpret_cast<uintptr_t>(in_re) | reinterpret_cast<uintptr_t>(in_im)) & 15) return fail(TFFT_ERR_ARG, "data pointers must be 16-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     for (int sl = 0; sl < p->slabs; ++sl) {
-      rc = dist_launch_col(p, sl, in_re, in_im, s);
+      rc = dist_launch_col(Launch::run(stream), p, sl, in_re, in_im);
       if (rc) return rc;
       TFFT_HIP(hipEventRecord(p->slab_done[static_cast<size_t>(sl)], s));
       TFFT_HIP(hipStreamWaitEvent(p->comm_stream, p->slab_done[static_cast<size_t>(sl)], 0));

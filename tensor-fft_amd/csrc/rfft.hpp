@@ -270,38 +270,27 @@ inline uint32_t rgrid(const tfft_rplan* r) {
   return static_cast<uint32_t>(std::min<uint64_t>((threads + rfft::kBlock - 1) / rfft::kBlock, static_cast<uint64_t>(r->num_cus) * 16));
 }
 
-int launch_fused_r2c(const tfft_rplan* r, const void* in, void* out_re, void* out_im, hipStream_t s) {
+int launch_fused_r2c(const Launch& L, const tfft_rplan* r, const void* in, void* out_re, void* out_im) {
   const tfft_plan* const p = r->fwd;
   uint32_t live, grid;
   k4096_shape(p, live, grid);
   const k4096::RealOut ro{r->sstride, (r->batch & 1) ? static_cast<uint32_t>(r->pairs - 1) : 0xffffffffu};
   constexpr int V = k4096::kStageOut | k4096::kNonTemporal;
-  TFFT_LAUNCH((k4096::fft4096_kernel<V, false, true>), kname("k4096::fft4096_kernel", V, false, true), dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s,
-              static_cast<const uint16_t*>(in), static_cast<const uint16_t*>(in) + r->rstride, static_cast<uint16_t*>(out_re),
-              static_cast<uint16_t*>(out_im), p->in_map, p->out_map, static_cast<uint32_t>(p->batch), live,
-              static_cast<const uint8_t*>(p->d_tables), p->otw, ro);
-  return TFFT_OK;
+  return launch(L, p->device, k4096::fft4096_kernel<V, false, true>, kname("k4096::fft4096_kernel", V, false, true), dim3(grid), dim3(k4096::kThreads),
+                k4096::kLdsBytes, static_cast<const uint16_t*>(in), static_cast<const uint16_t*>(in) + r->rstride, static_cast<uint16_t*>(out_re),
+                static_cast<uint16_t*>(out_im), p->in_map, p->out_map, static_cast<uint32_t>(p->batch), live,
+                static_cast<const uint8_t*>(p->d_tables), p->otw, ro);
 }
 
 // the split / merge pass of a real-input plan (non-temporal accesses unless the plan's cache policy says plain)
-void launch_split(const tfft_rplan* r, const rfft::SplitArgs& a, hipStream_t s) {
-  TFFT_NOTE_KERNEL(r->plain_acc ? reinterpret_cast<const void*>(rfft::split_kernel<false>) : reinterpret_cast<const void*>(rfft::split_kernel<true>),
-                   kname("rfft::split_kernel", !r->plain_acc));
-  if (g_prepare) return;
-  if (r->plain_acc)
-    hipLaunchKernelGGL(rfft::split_kernel<false>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL(rfft::split_kernel<true>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
+int launch_split(const Launch& L, const tfft_rplan* r, const rfft::SplitArgs& a) {
+  if (r->plain_acc) return launch(L, r->device, rfft::split_kernel<false>, kname("rfft::split_kernel", false), dim3(rgrid(r)), dim3(rfft::kBlock), 0, a);
+  return launch(L, r->device, rfft::split_kernel<true>, kname("rfft::split_kernel", true), dim3(rgrid(r)), dim3(rfft::kBlock), 0, a);
 }
 
-void launch_merge(const tfft_rplan* r, const rfft::MergeArgs& a, hipStream_t s) {
-  TFFT_NOTE_KERNEL(r->plain_acc ? reinterpret_cast<const void*>(rfft::merge_kernel<false>) : reinterpret_cast<const void*>(rfft::merge_kernel<true>),
-                   kname("rfft::merge_kernel", !r->plain_acc));
-  if (g_prepare) return;
-  if (r->plain_acc)
-    hipLaunchKernelGGL(rfft::merge_kernel<false>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL(rfft::merge_kernel<true>, dim3(rgrid(r)), dim3(rfft::kBlock), 0, s, a);
+int launch_merge(const Launch& L, const tfft_rplan* r, const rfft::MergeArgs& a) {
+  if (r->plain_acc) return launch(L, r->device, rfft::merge_kernel<false>, kname("rfft::merge_kernel", false), dim3(rgrid(r)), dim3(rfft::kBlock), 0, a);
+  return launch(L, r->device, rfft::merge_kernel<true>, kname("rfft::merge_kernel", true), dim3(rgrid(r)), dim3(rfft::kBlock), 0, a);
 }
 
 void rplan_free(tfft_rplan* r) {
@@ -380,10 +369,8 @@ int tfft_rplan_create(uint64_t n, uint64_t batch, int device_id, const tfft_plan
   off += rpart(std::max(tfft_plan_workspace_bytes(r->fwd_tail), tfft_plan_workspace_bytes(r->inv_tail)));
   r->ws_need = off;
   if (r->fused) {   // LDS opt-in of the fused kernel now, so that an execution is launches only
-    uint8_t* const fake = reinterpret_cast<uint8_t*>(uintptr_t{1} << 20);     // never dereferenced
-    g_prepare = true;
-    rc = launch_fused_r2c(r, fake, fake, fake, nullptr);
-    g_prepare = false;
+    const WalkPtrs f = walk_ptrs(0);
+    rc = launch_fused_r2c(Launch::opt_in(), r, f.in_re, f.out_re, f.out_im);
     if (rc) return bail(rc);
   }
   *out = r;
@@ -422,14 +409,14 @@ int tfft_rplan_kernels(const tfft_rplan* r, int c2r, char* buf, size_t bytes) {
   std::vector<std::string> names;
   int rc = TFFT_OK;
   if (!c2r && r->fused) {
-    uint8_t* const fake = reinterpret_cast<uint8_t*>(uintptr_t{1} << 20);     // never dereferenced
-    rc = record_walk(names, [&] { return launch_fused_r2c(r, fake, fake, fake, nullptr); });
+    const WalkPtrs f = walk_ptrs(0);
+    rc = record_walk(names, [&](const Launch& L) { return launch_fused_r2c(L, r, f.in_re, f.out_re, f.out_im); });
   } else if (!c2r) {
     for (const tfft_plan* sub : {r->fwd, r->fwd_tail})
       if (sub && rc == TFFT_OK) rc = record_kernels(sub, false, names);
-    if (rc == TFFT_OK) rc = record_walk(names, [&] { launch_split(r, rfft::SplitArgs{}, nullptr); return TFFT_OK; });
+    if (rc == TFFT_OK) rc = record_walk(names, [&](const Launch& L) { return launch_split(L, r, rfft::SplitArgs{}); });
   } else {
-    rc = record_walk(names, [&] { launch_merge(r, rfft::MergeArgs{}, nullptr); return TFFT_OK; });
+    rc = record_walk(names, [&](const Launch& L) { return launch_merge(L, r, rfft::MergeArgs{}); });
     for (const tfft_plan* sub : {r->inv, r->inv_tail})
       if (sub && rc == TFFT_OK) rc = record_kernels(sub, false, names);
   }
@@ -466,9 +453,8 @@ int tfft_rplan_prepare(tfft_rplan* r) {
   int prev = 0;
   TFFT_HIP(hipGetDevice(&prev));
   TFFT_HIP(hipSetDevice(r->device));
-  const int rc = rplan_ensure_workspace(r);
-  (void)hipSetDevice(prev);
-  return rc;
+  const DeviceRestore restore{prev};
+  return rplan_ensure_workspace(r);
 }
 
 int tfft_exec_r2c(const tfft_rplan* rc_plan, const void* in, void* out_re, void* out_im, void* stream) {
@@ -477,9 +463,9 @@ int tfft_exec_r2c(const tfft_rplan* rc_plan, const void* in, void* out_re, void*
   tfft_rplan* const r = const_cast<tfft_rplan*>(rc_plan);
   int rc = rplan_check_ptrs(r, in, out_re, out_im, true);
   if (rc) return rc;
-  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const Launch L = Launch::run(stream);
   if (r->fused) {
-    rc = launch_fused_r2c(r, in, out_re, out_im, s);
+    rc = launch_fused_r2c(L, r, in, out_re, out_im);
     if (rc) return rc;
     TFFT_HIP(hipGetLastError());
     return TFFT_OK;
@@ -500,7 +486,8 @@ int tfft_exec_r2c(const tfft_rplan* rc_plan, const void* in, void* out_re, void*
   }
   const rfft::SplitArgs a{z, static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), n, r->sstride,
                           static_cast<uint32_t>(r->pairs), (r->batch & 1) ? static_cast<uint32_t>(r->pairs - 1) : 0xffffffffu};
-  launch_split(r, a, s);
+  rc = launch_split(L, r, a);
+  if (rc) return rc;
   TFFT_HIP(hipGetLastError());
   return TFFT_OK;
 }
@@ -513,12 +500,13 @@ int tfft_exec_c2r(const tfft_rplan* rc_plan, const void* in_re, const void* in_i
   if (rc) return rc;
   rc = rplan_ensure_workspace(r);
   if (rc) return rc;
-  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const Launch L = Launch::run(stream);
   uint16_t* const z = static_cast<uint16_t*>(r->ws);
   const uint64_t n = r->n, full = r->batch / 2;
   const rfft::MergeArgs a{static_cast<const uint16_t*>(in_re), static_cast<const uint16_t*>(in_im), z, n, r->sstride,
                           static_cast<uint32_t>(r->pairs), (r->batch & 1) ? static_cast<uint32_t>(r->pairs - 1) : 0xffffffffu};
-  launch_merge(r, a, s);
+  rc = launch_merge(L, r, a);
+  if (rc) return rc;
   TFFT_HIP(hipGetLastError());
   uint16_t* const y = static_cast<uint16_t*>(out);
   if (r->inv) {

@@ -23,7 +23,14 @@ The shapes are the smallest at which each property exists (tfft_plan_describe):
     2d-rows  8 x 65536 x 2, 2d-cols 65536 x 16 x 2: a row / column sub-plan with scratch of its own behind the intermediate
     conv-2^16  (2^16, 5 signals, 2 filters): the composed path, two transposed sub-plans sharing one scratch share
     real-2^18  2^18 x 3: an odd batch, tail sub-plans and the scratch plane
+    real-4096  4096 x 3: the fused real plan, one launch and no workspace
+
+Section 7 is about the other state between calls: how the launch logic runs. tfft_plan_kernels & co. walk the launch logic of an
+execution without launching; neither a walk that succeeds, nor one that fails half way, nor one on another thread may change what
+the next execution launches.
 """
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -484,4 +491,114 @@ def test_real_plan_with_sub_plan_scratch(tf):
     plan.r2c(x, eager, eager[h:])
     torch.cuda.synchronize()
     assert _same(eager, spec), "eager differs from the captured execution"
+    plan.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. listing a plan's kernels walks its launch logic without launching: it leaves nothing behind for the next execution
+# ---------------------------------------------------------------------------------------------------------------------
+def _listing_that_fails_inside_the_walk(tf):
+    """auto-3 with padded batch strides and a caller's workspace of one block, asked for its in-place kernels: the chain of three
+    passes would start from a copy of the [RE | IM] block, and launch_chain refuses the padded layout (TFFT_ERR_ARG) from inside the
+    recording walk, behind the workspace look-up and in front of the first kernel."""
+    n, batch, stride = 512, 3, 2 * 512 + 8
+    plan = tf.TfftPlan(n, batch, 0, in_batch_stride=stride, out_batch_stride=stride, preserve_input=True, variant=tf.capi.VARIANT_AUTOSORT_ONLY)
+    assert plan.workspace_bytes == batch * n * 4
+    plan.set_workspace(torch.zeros(plan.workspace_bytes // 2, dtype=torch.float16, device=DEV))
+    assert len(plan.kernels) == 3, plan.kernels                # the out-of-place walk of the same plan goes through
+    # (through the C ABI itself: a listing returns its line count or a positive error code, and the binding takes a 5 for five lines)
+    buf = ctypes.create_string_buffer(1 << 12)
+    rc = plan._lib.tfft_plan_kernels_in_place(plan._h, buf, len(buf))
+    assert rc == 5 and buf.value == b"", (rc, buf.value)                                          # TFFT_ERR_ARG, nothing listed
+    assert "[RE | IM] block layout" in tf.capi.last_error(), tf.capi.last_error()                 # ... from launch_chain
+    plan.close()
+
+
+@pytest.mark.parametrize("sid", ["auto-3", "col-2", "tr-out", "real-4096"])
+def test_listing_kernels_between_executions_changes_nothing(tf, sid):
+    """Execute (against fp64), list the kernels out of place and in place, run a listing that fails inside its walk, execute again
+    into a cleared buffer: the bits of the first execution, and the same listings as before."""
+    if sid == "real-4096":
+        n, batch = 4096, 3
+        plan = tf.TfftRealPlan(n, batch, 0)
+        assert plan.num_launches(False) == 1, plan.kernels(False)      # fused: the N = 4096 kernel alone
+        h, bins = plan.pitch, n // 2 + 1
+        rng = np.random.default_rng([26, n, batch])
+        xh = rng.uniform(-1, 1, (batch, n)).astype(np.float16)
+        ref = np.fft.rfft(xh.astype(np.float64), axis=1) / n
+        x, y = _dev(xh), torch.zeros(batch * 2 * h, dtype=torch.float16, device=DEV)
+        run = lambda out: plan.r2c(x, out, out[h:])                             # noqa: E731
+        listings = lambda: (plan.kernels(False), plan.kernels(True))            # noqa: E731
+
+        def check(out, what):
+            got = out.cpu().numpy().astype(np.float64).reshape(batch, 2, h)
+            worst = eb.check(got[:, 0, :bins], got[:, 1, :bins], ref.real, ref.imag, eb.K_REAL, rel_l2=eb.REL_L2, pairs=True, what=what)
+            print(f"{what}: worst {worst:.3f} ulp")
+    else:
+        plan = make_plan(tf, sid)
+        n, batch = plan.n, plan.batch
+        xin, fwd, _ = _data(tf, sid)
+        k = k_of(plan.kernels, {"kind": "c"})
+        x, y = _dev(xin), torch.zeros(batch * 2 * n, dtype=torch.float16, device=DEV)
+        run = lambda out: plan.exec(x, x[n:], out, out[n:])                     # noqa: E731
+        listings = lambda: (plan.kernels, plan.kernels_in_place)                # noqa: E731
+        check = lambda out, what: _check(out, fwd, batch, n, k, what)           # noqa: E731
+    run(y)
+    torch.cuda.synchronize()
+    check(y, f"{sid}: first execution")
+    before = listings()
+    assert all(before), before
+    _listing_that_fails_inside_the_walk(tf)
+    again = torch.zeros_like(y)
+    run(again)
+    torch.cuda.synchronize()
+    assert _same(again, y), "an execution after the listings differs from the one before them"
+    check(again, f"{sid}: execution after the listings")
+    assert listings() == before, "the listings changed"
+    plan.close()
+
+
+def test_listing_on_one_thread_does_not_reach_an_execution_on_another(tf):
+    """The single-pass plan that test_one_plan_from_several_host_threads shares, n = 4096 x 64: one thread lists its kernels 200
+    times while this one executes 20 times on a stream of its own into its own zeroed output. The bits of a quiet run, and the
+    same one-line listing every time: a walk is its caller's business alone."""
+    import threading
+
+    n, batch = 4096, 64
+    plan = tf.TfftPlan(n, batch, 0)
+    quiet_list = plan.kernels
+    assert plan.num_launches == 1 and len(quiet_list) == 1, quiet_list
+    rng = np.random.default_rng([27, n, batch])
+    xh = rng.uniform(-1, 1, (batch, 2, n)).astype(np.float16)
+    xc = xh[:, 0].astype(np.float64) + 1j * xh[:, 1].astype(np.float64)
+    x, quiet = _dev(xh), torch.zeros(batch * 2 * n, dtype=torch.float16, device=DEV)
+    plan.exec(x, x[n:], quiet, quiet[n:])
+    torch.cuda.synchronize()
+    _check(quiet, np.fft.fft(xc, axis=1) / n, batch, n, k_of(quiet_list, {"kind": "c"}), "4096 x 64: quiet run")
+    seen, errs = [], []
+    started = threading.Event()
+
+    def lister():
+        try:
+            for i in range(200):
+                seen.append(plan.kernels)
+                if i == 0:
+                    started.set()
+        except Exception as e:   # noqa: BLE001
+            errs.append(e)
+            started.set()
+
+    got = torch.zeros_like(quiet)
+    stream = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    t = threading.Thread(target=lister)
+    t.start()
+    started.wait()
+    for _ in range(20):
+        plan.exec(x, x[n:], got, got[n:], stream.cuda_stream)
+    stream.synchronize()
+    t.join()
+    assert not errs, errs
+    assert len(seen) == 200 and all(s == quiet_list for s in seen), [s for s in seen if s != quiet_list][:3]
+    assert _same(got, quiet), "an execution beside a listing thread differs from the quiet run"
     plan.close()
