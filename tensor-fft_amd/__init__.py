@@ -3,7 +3,7 @@
 Import name: ``tensor_fft_amd`` (see ``tensor_fft_amd.py`` at the repository
 root; the directory carries the upstream project's hyphen).
 
-Three layers, all thin:
+Four layers, all thin:
 
 * :mod:`.capi` — ctypes binding of the C ABI ``include/tfft.h`` in
   ``libtfft.so`` (hand-written HIP, built in-tree by ``__graft_entry__.build``).
@@ -11,6 +11,8 @@ Three layers, all thin:
   not gfx950, calls raise.
 * :mod:`.conv` — ctypes binding of the FFT convolution add-on ``include/tfft_conv.h`` in
   ``libtfft_conv.so`` (layered on ``libtfft.so``; same rule: no fallback).
+* :mod:`.lconv` — ctypes binding of the causal real convolution add-on ``include/tfft_lconv.h`` in
+  ``libtfft_lconv.so`` (layered on the other two; same rule: no fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -23,6 +25,8 @@ from .capi import (TfftError, TfftPlan, TfftPlan2D, TfftRealPlan, device_check, 
                    tuning_load, tuning_query, variant_check)
 from .conv import (TfftConvPlan, conv_cache_clear, conv_describe, conv_filter_slot, conv_lib_path, fftconv,  # noqa: F401
                    load_conv_library)
+from .lconv import (TfftCausalConvPlan, causal_conv, lconv_cache_clear, lconv_describe, lconv_fft_length, lconv_lib_path,  # noqa: F401
+                    lconv_spectrum_host, load_lconv_library)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -39,6 +43,8 @@ __all__ = [
     "TfftError", "TfftPlan", "TfftPlan2D", "TfftRealPlan", "device_check", "irfft", "rfft", "rplan_cache_clear", "rplan_describe", "rplan_spectrum_pitch", "lib_path", "load_library", "plan_cache_policy", "plan_default_variant", "plan_describe", "ref_create_plan",
     "synth_uniform", "transposed_n2", "variant_check", "kernel_list", "tuning_add", "tuning_clear", "tuning_load", "tuning_query",
     "TfftConvPlan", "conv_cache_clear", "conv_describe", "conv_filter_slot", "conv_lib_path", "fftconv", "load_conv_library",
+    "TfftCausalConvPlan", "causal_conv", "lconv_cache_clear", "lconv_describe", "lconv_fft_length", "lconv_lib_path", "lconv_spectrum_host",
+    "load_lconv_library",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]

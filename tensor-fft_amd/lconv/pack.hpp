@@ -1,0 +1,44 @@
+// pack.hpp — the two ends of the composed causal convolution (include/tfft_lconv.h): real sequences into the zero-padded
+// [RE n | IM n] blocks a tfft_conv_plan works on, and the kept samples back out. One thread per 16-byte chunk, grid-stride.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace lconv_copy {     // (not "lconv": <locale.h> owns that name at global scope)
+
+constexpr int kThreads = 256;
+typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+
+// blocks: item it = p * channels + c at + it * 2 n halves, n = 8 << log_n8: plane 0 = sequence (2p, c), plane 1 = (2p + 1, c),
+// zeros from sample 8 * chunks on and for a row that does not exist. total = items * 2 * (n / 8) chunks. The blocks are read
+// right back by the sub-plan: plain stores; the sequences are touched once: nt loads.
+__global__ __launch_bounds__(kThreads) void pack_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ blocks, uint64_t in_seq,
+                                                        uint32_t rows, uint32_t channels, uint32_t chunks, uint32_t log_n8, uint64_t total) {
+  const uint64_t step = static_cast<uint64_t>(gridDim.x) * kThreads;
+  for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x; t < total; t += step) {
+    const uint64_t j = t & ((uint64_t{1} << log_n8) - 1);
+    const uint64_t plane = t >> log_n8;                          // 2 it + (0: RE, 1: IM)
+    const uint64_t it = plane >> 1, p = it / channels, c = it - p * channels;
+    const uint64_t row = 2 * p + (plane & 1);
+    u4 v = {0, 0, 0, 0};
+    if (j < chunks && row < rows) v = __builtin_nontemporal_load(reinterpret_cast<const u4*>(in + (row * channels + c) * in_seq) + j);
+    reinterpret_cast<u4*>(blocks)[t] = v;
+  }
+}
+
+// out: sequence s = b * channels + c at + s * out_seq halves takes the first 8 * chunks samples of plane b & 1 of item
+// (b >> 1) * channels + c. total = rows * channels * chunks.
+__global__ __launch_bounds__(kThreads) void crop_kernel(const uint16_t* __restrict__ blocks, uint16_t* __restrict__ out, uint64_t out_seq,
+                                                        uint32_t channels, uint32_t chunks, uint32_t log_n8, uint64_t total) {
+  const uint64_t step = static_cast<uint64_t>(gridDim.x) * kThreads;
+  for (uint64_t t = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x; t < total; t += step) {
+    const uint64_t s = t / chunks, j = t - s * chunks;
+    const uint64_t b = s / channels, c = s - b * channels;
+    const uint64_t plane = 2 * ((b >> 1) * channels + c) + (b & 1);
+    const u4 v = reinterpret_cast<const u4*>(blocks)[(plane << log_n8) + j];
+    __builtin_nontemporal_store(v, reinterpret_cast<u4*>(out + s * out_seq) + j);
+  }
+}
+
+}  // namespace lconv_copy
