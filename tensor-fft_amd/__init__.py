@@ -3,7 +3,7 @@
 Import name: ``tensor_fft_amd`` (see ``tensor_fft_amd.py`` at the repository
 root; the directory carries the upstream project's hyphen).
 
-Four layers, all thin:
+Five layers, all thin:
 
 * :mod:`.capi` — ctypes binding of the C ABI ``include/tfft.h`` in
   ``libtfft.so`` (hand-written HIP, built in-tree by ``__graft_entry__.build``).
@@ -13,6 +13,8 @@ Four layers, all thin:
   ``libtfft_conv.so`` (layered on ``libtfft.so``; same rule: no fallback).
 * :mod:`.lconv` — ctypes binding of the causal real convolution add-on ``include/tfft_lconv.h`` in
   ``libtfft_lconv.so`` (layered on the other two; same rule: no fallback).
+* :mod:`.gconv` — ctypes binding of the gated causal convolution add-on ``include/tfft_gconv.h`` in
+  ``libtfft_gconv.so`` (layered on ``libtfft_conv.so`` and ``libtfft.so``; same rule: no fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -27,6 +29,8 @@ from .conv import (TfftConvPlan, conv_cache_clear, conv_describe, conv_filter_sl
                    load_conv_library)
 from .lconv import (TfftCausalConvPlan, causal_conv, lconv_cache_clear, lconv_describe, lconv_fft_length, lconv_lib_path,  # noqa: F401
                     lconv_spectrum_host, load_lconv_library)
+from .gconv import (TfftGatedConvPlan, gated_causal_conv, gconv_cache_clear, gconv_describe, gconv_fft_length, gconv_lib_path,  # noqa: F401
+                    gconv_spectrum_host, load_gconv_library)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -45,6 +49,8 @@ __all__ = [
     "TfftConvPlan", "conv_cache_clear", "conv_describe", "conv_filter_slot", "conv_lib_path", "fftconv", "load_conv_library",
     "TfftCausalConvPlan", "causal_conv", "lconv_cache_clear", "lconv_describe", "lconv_fft_length", "lconv_lib_path", "lconv_spectrum_host",
     "load_lconv_library",
+    "TfftGatedConvPlan", "gated_causal_conv", "gconv_cache_clear", "gconv_describe", "gconv_fft_length", "gconv_lib_path", "gconv_spectrum_host",
+    "load_gconv_library",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]
