@@ -3,7 +3,7 @@
 Import name: ``tensor_fft_amd`` (see ``tensor_fft_amd.py`` at the repository
 root; the directory carries the upstream project's hyphen).
 
-Five layers, all thin:
+Six layers, all thin:
 
 * :mod:`.capi` — ctypes binding of the C ABI ``include/tfft.h`` in
   ``libtfft.so`` (hand-written HIP, built in-tree by ``__graft_entry__.build``).
@@ -15,6 +15,8 @@ Five layers, all thin:
   ``libtfft_lconv.so`` (layered on the other two; same rule: no fallback).
 * :mod:`.gconv` — ctypes binding of the gated causal convolution add-on ``include/tfft_gconv.h`` in
   ``libtfft_gconv.so`` (layered on ``libtfft_conv.so`` and ``libtfft.so``; same rule: no fallback).
+* :mod:`.sconv` — ctypes binding of the overlap-save causal convolution add-on ``include/tfft_sconv.h`` in
+  ``libtfft_sconv.so`` (any sequence length in one kernel; layered on ``libtfft_conv.so`` and ``libtfft.so``; no fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -31,6 +33,8 @@ from .lconv import (TfftCausalConvPlan, causal_conv, lconv_cache_clear, lconv_de
                     lconv_spectrum_host, load_lconv_library)
 from .gconv import (TfftGatedConvPlan, gated_causal_conv, gconv_cache_clear, gconv_describe, gconv_fft_length, gconv_lib_path,  # noqa: F401
                     gconv_spectrum_host, load_gconv_library)
+from .sconv import (TfftLongConvPlan, load_sconv_library, long_causal_conv, sconv_cache_clear, sconv_describe, sconv_geometry,  # noqa: F401
+                    sconv_lib_path)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -51,6 +55,7 @@ __all__ = [
     "load_lconv_library",
     "TfftGatedConvPlan", "gated_causal_conv", "gconv_cache_clear", "gconv_describe", "gconv_fft_length", "gconv_lib_path", "gconv_spectrum_host",
     "load_gconv_library",
+    "TfftLongConvPlan", "load_sconv_library", "long_causal_conv", "sconv_cache_clear", "sconv_describe", "sconv_geometry", "sconv_lib_path",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]
