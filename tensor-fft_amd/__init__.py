@@ -3,7 +3,7 @@
 Import name: ``tensor_fft_amd`` (see ``tensor_fft_amd.py`` at the repository
 root; the directory carries the upstream project's hyphen).
 
-Six layers, all thin:
+Seven layers, all thin:
 
 * :mod:`.capi` — ctypes binding of the C ABI ``include/tfft.h`` in
   ``libtfft.so`` (hand-written HIP, built in-tree by ``__graft_entry__.build``).
@@ -17,6 +17,9 @@ Six layers, all thin:
   ``libtfft_gconv.so`` (layered on ``libtfft_conv.so`` and ``libtfft.so``; same rule: no fallback).
 * :mod:`.sconv` — ctypes binding of the overlap-save causal convolution add-on ``include/tfft_sconv.h`` in
   ``libtfft_sconv.so`` (any sequence length in one kernel; layered on ``libtfft_conv.so`` and ``libtfft.so``; no fallback).
+* :mod:`.bconv` — ctypes binding of the gradient add-on ``include/tfft_bconv.h`` in ``libtfft_bconv.so`` (the input and the tap
+  gradient of the overlap-save convolution, and the ``torch.autograd`` hook over them; layered on ``libtfft_conv.so`` and
+  ``libtfft.so``; no fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -35,6 +38,8 @@ from .gconv import (TfftGatedConvPlan, gated_causal_conv, gconv_cache_clear, gco
                     gconv_spectrum_host, load_gconv_library)
 from .sconv import (TfftLongConvPlan, load_sconv_library, long_causal_conv, sconv_cache_clear, sconv_describe, sconv_geometry,  # noqa: F401
                     sconv_lib_path)
+from .bconv import (TfftLongConvGradPlan, bconv_cache_clear, bconv_describe, bconv_geometry, bconv_lib_path,  # noqa: F401
+                    differentiable_long_causal_conv, load_bconv_library, long_causal_conv_input_grad, long_causal_conv_tap_grad)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -56,6 +61,8 @@ __all__ = [
     "TfftGatedConvPlan", "gated_causal_conv", "gconv_cache_clear", "gconv_describe", "gconv_fft_length", "gconv_lib_path", "gconv_spectrum_host",
     "load_gconv_library",
     "TfftLongConvPlan", "load_sconv_library", "long_causal_conv", "sconv_cache_clear", "sconv_describe", "sconv_geometry", "sconv_lib_path",
+    "TfftLongConvGradPlan", "bconv_cache_clear", "bconv_describe", "bconv_geometry", "bconv_lib_path", "differentiable_long_causal_conv",
+    "load_bconv_library", "long_causal_conv_input_grad", "long_causal_conv_tap_grad",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]
