@@ -3,7 +3,7 @@
 Import name: ``tensor_fft_amd`` (see ``tensor_fft_amd.py`` at the repository
 root; the directory carries the upstream project's hyphen).
 
-Seven layers, all thin:
+Eight layers, all thin:
 
 * :mod:`.capi` — ctypes binding of the C ABI ``include/tfft.h`` in
   ``libtfft.so`` (hand-written HIP, built in-tree by ``__graft_entry__.build``).
@@ -20,6 +20,9 @@ Seven layers, all thin:
 * :mod:`.bconv` — ctypes binding of the gradient add-on ``include/tfft_bconv.h`` in ``libtfft_bconv.so`` (the input and the tap
   gradient of the overlap-save convolution, and the ``torch.autograd`` hook over them; layered on ``libtfft_conv.so`` and
   ``libtfft.so``; no fallback).
+* :mod:`.gsconv` — ctypes binding of the gated overlap-save convolution add-on ``include/tfft_gsconv.h`` in ``libtfft_gsconv.so``
+  (the gated operator of :mod:`.gconv` at any sequence length in one kernel; layered on ``libtfft_conv.so`` and ``libtfft.so``; no
+  fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -40,6 +43,8 @@ from .sconv import (TfftLongConvPlan, load_sconv_library, long_causal_conv, scon
                     sconv_lib_path)
 from .bconv import (TfftLongConvGradPlan, bconv_cache_clear, bconv_describe, bconv_geometry, bconv_lib_path,  # noqa: F401
                     differentiable_long_causal_conv, load_bconv_library, long_causal_conv_input_grad, long_causal_conv_tap_grad)
+from .gsconv import (TfftGatedLongConvPlan, gated_long_causal_conv, gsconv_cache_clear, gsconv_describe, gsconv_geometry,  # noqa: F401
+                     gsconv_lib_path, load_gsconv_library)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -63,6 +68,8 @@ __all__ = [
     "TfftLongConvPlan", "load_sconv_library", "long_causal_conv", "sconv_cache_clear", "sconv_describe", "sconv_geometry", "sconv_lib_path",
     "TfftLongConvGradPlan", "bconv_cache_clear", "bconv_describe", "bconv_geometry", "bconv_lib_path", "differentiable_long_causal_conv",
     "load_bconv_library", "long_causal_conv_input_grad", "long_causal_conv_tap_grad",
+    "TfftGatedLongConvPlan", "gated_long_causal_conv", "gsconv_cache_clear", "gsconv_describe", "gsconv_geometry", "gsconv_lib_path",
+    "load_gsconv_library",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]

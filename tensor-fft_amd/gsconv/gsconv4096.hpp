@@ -1,0 +1,391 @@
+// gsconv4096.hpp — fused GATED overlap-save causal convolution of REAL sequences of any length for gfx950:
+//
+//     y = g (.) ( h' * (p (.) x) )          h' = the taps with the skip weight added to tap 0 (folded into the spectrum on the host)
+//
+// sconv/sconv4096.hpp with gconv/gconv4096.hpp's two ends: the middle is sconv4096_kernel's, statement by statement (same tables,
+// same three MFMA stages twice, same fp32 filter multiply with its one rounding, same filter image in filter_slot order, same
+// exchanged-plane write-back and stage-out swizzle, same LDS image and launch shape). A sequence is cut into segments of `hop` =
+// 4096 - `halo` output samples; segment s transforms the 4096-sample window that starts at sample s * hop - halo and keeps the
+// samples behind the halo.
+//
+//   load    item (p, s, c): slot l of 1-KiB block mm holds window chunk j = 64 mm + (l ^ 2 mm), whose SOURCE chunk is
+//           sc = s * hop / 8 - halo / 8 + j, signed. Pre = false: sconv4096's load, statement by statement (LDS-DMA of the chunks in
+//           [0, L / 8), zero fill of every other slot). Pre = true: source chunk sc of x AND of the gate p come in through registers
+//           (the gate is indexed by the source chunk, never by the window chunk: a segment re-reads the gate over its halo just as it
+//           re-reads x), are multiplied (one packed binary16 multiply per pair of samples: round to nearest even, subnormals kept) and
+//           written into the slot the DMA would have filled (ds_write_b128); no LDS-DMA is issued at all. A plane's 16 loads are
+//           issued before its first product is formed and none sits under a per-lane branch: a lane whose sc lies outside [0, L / 8)
+//           loads chunk max(s * hop / 8 - halo / 8, 0) of the same sequence instead, which this item reads anyway and which is
+//           always below L / 8, and a select then writes the product or zero. Nothing outside [0, L) of x or p is read; a zero
+//           partner's plane is all zero fill and neither its sequence nor its gate is read.
+//   store   staged chunk j = 64 i + l goes to OUTPUT chunk oc = s * hop / 8 + j - halo / 8 where j >= halo / 8 and oc < L / 8.
+//           Post = true: chunk oc of g is loaded, multiplied with the staged result (packed binary16 multiply) and the product
+//           stored non-temporally. The RE plane's 8 gate loads are issued between the two passes and fly under pass 1 (32
+//           registers); the IM plane's are issued together behind pass 1, ahead of the RE plane's stores. None sits under a per-lane
+//           branch: a lane that stores nothing loads chunk s * hop / 8 of the same gate sequence, which the item always stores
+//           (window chunk halo / 8; s * hop < L for every segment). Nothing beyond sample L of g is read.
+//
+// The stage code is restated on the k4096 helpers, as sconv4096.hpp and gconv4096.hpp restate it: including either would emit its
+// kernel into this code object.
+#pragma once
+
+#include "../csrc/k4096.hpp"
+
+namespace gsconv4096 {
+
+using k4096::f4;
+using k4096::h8;
+using k4096::s4;
+using k4096::u2;
+using k4096::u4;
+
+// slot of bin k in a plane of the filter image: conv4096::filter_slot / sconv4096::filter_slot restated.
+// tests/test_gpu_gsconv.py holds it to the shipped kernel: conv4096_kernel, given the plan's natural-order spectrum and the gated
+// windows built on the host, must reproduce this kernel's output bit for bit.
+__host__ __device__ constexpr uint32_t filter_slot(uint32_t k) {
+  const uint32_t k0 = k & 15, k1 = (k >> 4) & 15, k2 = k >> 8;
+  const uint32_t half = k0 >> 3, j = k0 & 7, g = k2 >> 2, r2 = k2 & 3;
+  return ((half * 4 + r2) * 64 + 16 * g + k1) * 8 + j;
+}
+
+// eight binary16 products, each rounded once (v_pk_mul_f16 x 4)
+__device__ __forceinline__ u4 mul8(u4 a, u4 b) { return __builtin_bit_cast(u4, __builtin_bit_cast(h8, a) * __builtin_bit_cast(h8, b)); }
+
+// sconv4096::dma_chunk: one plane's share of 1-KiB block mm by LDS-DMA, nt, under the lanes' own predicate
+__device__ __forceinline__ void dma_chunk(const uint8_t* src, uint32_t dst) {
+  uint32_t keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %2\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off nt\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(src), "s"(dst)
+      : "memory");
+}
+
+// what the kernel needs of a plan's geometry, in 16-byte chunks (8 samples): L / 8, halo / 8, hop / 8 = 512 - halo / 8, and the
+// segments per sequence. All below 2^23 (L <= 2^26), so the signed 32-bit arithmetic below cannot overflow.
+struct geometry {
+  int32_t chunks, halo, hop, segments;
+};
+
+// item -> (pair p, segment s, channel c): item = (p * segments + s) * channels + c, wave-uniform
+__device__ __forceinline__ void split_item(uint32_t it, uint32_t channels, const geometry& geo, uint32_t& p, int32_t& s, uint32_t& c) {
+  const uint32_t q = it / channels;
+  c = it - q * channels;
+  p = q / static_cast<uint32_t>(geo.segments);
+  s = static_cast<int32_t>(q - p * static_cast<uint32_t>(geo.segments));
+}
+
+// Builds the image of item `it` in the wave's LDS region: p (.) x in the slots whose source chunk lies in [0, L / 8), zeros
+// everywhere else. Whatever it issues (zero writes, DMA, product writes) is retired by the s_waitcnt vmcnt(0) / lgkmcnt(0) that
+// follow it in the kernel's loop, one phase before stage 1 reads the image.
+template <bool Pre>
+__device__ __forceinline__ void load_item(const uint16_t* in, const uint16_t* pre, uint64_t in_seq, uint64_t pre_seq, uint32_t rows,
+                                          uint32_t channels, const geometry& geo, uint32_t it, uint8_t* wl, uint32_t wl_off, int lane) {
+  uint32_t p, c;
+  int32_t s;
+  split_item(it, channels, geo, p, s, c);
+  const bool has_im = 2 * p + 1 < rows;                  // wave-uniform
+  const int32_t first = s * geo.hop - geo.halo;          // source chunk of window chunk 0: negative in front of sample 0
+  const uint64_t seq = static_cast<uint64_t>(2 * p) * channels + c;
+  const uint8_t* const src_re = reinterpret_cast<const uint8_t*>(in + seq * in_seq);
+  const uint8_t* const src_im = src_re + 2 * static_cast<uint64_t>(channels) * in_seq;
+  const u4 zero = {0, 0, 0, 0};
+  if constexpr (Pre) {
+    const uint8_t* const gate_re = reinterpret_cast<const uint8_t*>(pre + seq * pre_seq);
+    const uint8_t* const gate_im = gate_re + 2 * static_cast<uint64_t>(channels) * pre_seq;
+    // the chunk the lanes without a source chunk load instead: the first source chunk of the window that lies inside the sequence
+    // (s * hop < L for every segment, so it is below L / 8), one this item reads anyway
+    const int32_t spare = first > 0 ? first : 0;
+    // A plane's 16 loads are issued before its first product is formed, so a plane pays one HBM round trip, as its 8 DMAs do in the
+    // ungated load. No load sits under a branch, which would pin a wait to it. The test is on the source chunk, not the lane or the
+    // window chunk: the slots are swizzled and the window is offset; the gate chunk is the data chunk's.
+    auto plane = [&](const uint8_t* src, const uint8_t* gate, uint8_t* dst) {
+      u4 xv[8], gv[8];
+#pragma unroll
+      for (int mm = 0; mm < 8; ++mm) {
+        const int32_t chunk = first + (mm * 64 + (lane ^ (2 * mm)));     // the source chunk slot `lane` of block mm holds
+        const uint32_t off = static_cast<uint32_t>(chunk >= 0 && chunk < geo.chunks ? chunk : spare) * 16u;       // below 2^27
+        xv[mm] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(src + off));
+        gv[mm] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(gate + off));
+      }
+#pragma unroll
+      for (int mm = 0; mm < 8; ++mm) {
+        const int32_t chunk = first + (mm * 64 + (lane ^ (2 * mm)));
+        const u4 prod = mul8(xv[mm], gv[mm]);
+        *reinterpret_cast<u4*>(dst + mm * 1024 + lane * 16) = chunk >= 0 && chunk < geo.chunks ? prod : zero;
+      }
+    };
+    plane(src_re, gate_re, wl);
+    if (has_im) {
+      plane(src_im, gate_im, wl + 8192);
+    } else {
+#pragma unroll
+      for (int mm = 0; mm < 8; ++mm) *reinterpret_cast<u4*>(wl + 8192 + mm * 1024 + lane * 16) = zero;
+    }
+  } else {
+#pragma unroll
+    for (int mm = 0; mm < 8; ++mm) {
+      const int32_t chunk = first + (mm * 64 + (lane ^ (2 * mm)));     // the source chunk slot `lane` of block mm holds
+      uint8_t* const slot = wl + mm * 1024 + lane * 16;
+      // The test is on the chunk, not the lane: the slots are swizzled. A block with no chunk inside the sequence has no lane left in
+      // the first branch, which the wave then skips as a whole: no DMA is issued for it.
+      if (chunk >= 0 && chunk < geo.chunks) {
+        const int64_t byte = static_cast<int64_t>(chunk) * 16;
+        dma_chunk(src_re + byte, wl_off + mm * 1024);
+        if (has_im)
+          dma_chunk(src_im + byte, wl_off + 8192 + mm * 1024);
+        else
+          *reinterpret_cast<u4*>(slot + 8192) = zero;
+      } else {
+        *reinterpret_cast<u4*>(slot) = zero;
+        *reinterpret_cast<u4*>(slot + 8192) = zero;
+      }
+    }
+  }
+}
+
+// in / pre / post / out: real binary16, sequence (b, c) at + (b * channels + c) * its seq stride halves, 8 * geo.chunks samples
+// each; pre is read only when Pre, post only when Post. items = ceil(rows / 2) * geo.segments * channels, item
+// (p * segments + s) * channels + c. tables: the first k4096::kOffF1n bytes of a k4096::build_tables() blob. filt: filter images as
+// conv4096_kernel takes them, channel c at + c * 8192 halves. in, pre and post may alias each other: no __restrict__ on them.
+template <bool Pre, bool Post>
+__global__ __launch_bounds__(k4096::kThreads, 2) void gsconv4096_kernel(
+    const uint16_t* in, const uint16_t* pre, const uint16_t* post, uint16_t* out, uint64_t in_seq, uint64_t pre_seq, uint64_t post_seq,
+    uint64_t out_seq, uint32_t rows, uint32_t channels, geometry geo, uint32_t items, uint32_t live,
+    const uint8_t* __restrict__ tables, const uint16_t* __restrict__ filt) {
+  using namespace k4096;
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  uint8_t* const wl = lds + kLdsTableBytes + wave * kLdsWaveBytes;
+  const uint32_t wl_off = __builtin_amdgcn_readfirstlane(
+      static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint8_t*)wl)));
+
+  // live waves and the stride over the items: as conv4096_kernel
+  const uint32_t stride_b = gridDim.x * live;
+  uint32_t b = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(wave) < live ? blockIdx.x * live + wave : items);
+
+  for (int i = tid; i < kLdsTableBytes / 16; i += kThreads)
+    reinterpret_cast<u4*>(lds)[i] = reinterpret_cast<const u4*>(tables + kOffG)[i];
+
+  const h8 f_re = *reinterpret_cast<const h8*>(tables + kOffF1 + lane * 32);
+  const h8 f_im = *reinterpret_cast<const h8*>(tables + kOffF1 + lane * 32 + 16);
+  const f4 tw_re = *reinterpret_cast<const f4*>(tables + kOffTw + lane * 32);
+  const f4 tw_im = *reinterpret_cast<const f4*>(tables + kOffTw + lane * 32 + 16);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // table loads retired: vmcnt below counts only loop traffic
+  __syncthreads();
+  if (b >= items) return;
+
+  const uint8_t* const g_tab = lds + lane * 16;
+  const uint8_t* const h_tab = lds + 16384 + lane * 16;
+
+  // transposed-read geometry of stage 1 (k4096.hpp)
+  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  const int m = q + 4 * (g & 1), bb = g >> 1;
+  uint8_t* const tr_base = wl + m * 1024 + bb * 512 + 8 * p;
+
+  // stages 1 -> 3 on the wave's LDS image: conv4096_kernel's, statement by statement
+  auto transform = [&](auto&& mul, auto&& sink) {
+    uint32_t pr[8][4], pi[8][4];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      f4 dre[2], dim[2];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int n1 = 2 * t + e;
+        uint8_t* a = tr_base + 32 * (n1 ^ m);
+        const s4 xr = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(a));
+        const s4 xi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(a + 8192));
+        const u4 raw = {__builtin_bit_cast(u2, xr).x, __builtin_bit_cast(u2, xr).y, __builtin_bit_cast(u2, xi).x, __builtin_bit_cast(u2, xi).y};
+        const h8 x = __builtin_bit_cast(h8, raw);
+        dre[e] = mfma(f_re, x);
+        dim[e] = mfma(f_im, x);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        pr[t][r] = pk(dre[0][r], dre[1][r]);
+        pi[t][r] = pk(dim[0][r], dim[1][r]);
+      }
+    }
+#pragma unroll
+    for (int pp = 0; pp < 2; ++pp)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        transpose4(pr[0 + pp][r], pr[2 + pp][r], pr[4 + pp][r], pr[6 + pp][r]);
+        transpose4(pi[0 + pp][r], pi[2 + pp][r], pi[4 + pp][r], pi[6 + pp][r]);
+      }
+    auto tile23 = [&](int k0, f4& o_re, f4& o_im) {
+      const int a = k0 >> 2, r = k0 & 3;
+      const u4 araw = {pr[2 * a][r], pr[2 * a + 1][r], pi[2 * a][r], pi[2 * a + 1][r]};
+      const h8 aop = __builtin_bit_cast(h8, araw);
+      const u4 graw = *reinterpret_cast<const u4*>(g_tab + k0 * 1024);
+      const f4 e_re = mfma(aop, __builtin_bit_cast(h8, graw));
+      const f4 e_im = mfma(aop, im_form(graw));
+      // scalar fp32 on purpose, see tile23 of k4096.hpp
+      f4 t_re, t_im;
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) {
+        t_re[r4] = __builtin_fmaf(e_re[r4], tw_re[r4], -(e_im[r4] * tw_im[r4]));
+        t_im[r4] = __builtin_fmaf(e_re[r4], tw_im[r4], e_im[r4] * tw_re[r4]);
+      }
+      const u4 braw = {pk(t_re[0], t_re[1]), pk(t_re[2], t_re[3]), pk(t_im[0], t_im[1]), pk(t_im[2], t_im[3])};
+      const h8 bop = __builtin_bit_cast(h8, braw);
+      const u4 hraw = *reinterpret_cast<const u4*>(h_tab + k0 * 1024);
+      o_re = mfma(__builtin_bit_cast(h8, hraw), bop);   // o[r2] = X[k0 + 16 k1 + 256 (4g + r2)]
+      o_im = mfma(im_form(hraw), bop);
+      mul(k0, o_re, o_im);
+    };
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      uint32_t ore[4][4], oim[4][4];   // [r2][k0 pair within this half]
+#pragma unroll
+      for (int kp = 0; kp < 4; ++kp) {
+        f4 e_re, e_im, o_re, o_im;
+        tile23(8 * half + 2 * kp, e_re, e_im);
+        tile23(8 * half + 2 * kp + 1, o_re, o_im);
+#pragma unroll
+        for (int r2 = 0; r2 < 4; ++r2) {
+          ore[r2][kp] = pk(e_re[r2], o_re[r2]);
+          oim[r2][kp] = pk(e_im[r2], o_im[r2]);
+        }
+      }
+#pragma unroll
+      for (int r2 = 0; r2 < 4; ++r2) {
+        const u4 vr = {ore[r2][0], ore[r2][1], ore[r2][2], ore[r2][3]};
+        const u4 vi = {oim[r2][0], oim[r2][1], oim[r2][2], oim[r2][3]};
+        sink(half, r2, vr, vi);
+      }
+    }
+  };
+
+  // The order of events of sconv4096_kernel: an item's image is built at the top of the loop, once the previous item's image has
+  // been read out (the lgkmcnt(0) at the bottom), and the waits follow in straight-line code, so every path from an LDS-DMA to the
+  // end of the program passes an s_waitcnt vmcnt(0) whatever shape the compiler gives the loop's latch.
+  do {
+    load_item<Pre>(in, pre, in_seq, pre_seq, rows, channels, geo, b, wl, wl_off, lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the item's DMA has landed (Pre: its loads are the compiler's to count) ...
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // ... and so have its zero fill and products, before stage 1 reads them
+
+    // this item's filter values: [half][r2] vectors of 8 bins, RE and IM (plain cached loads; they fly under stage 1)
+    const uint16_t* const fimg = filt + static_cast<uint64_t>(b % channels) * 8192u + 8u * lane;
+    u4 hre[2][4], him[2][4];
+#pragma unroll
+    for (int half = 0; half < 2; ++half)
+#pragma unroll
+      for (int r2 = 0; r2 < 4; ++r2) {
+        hre[half][r2] = *reinterpret_cast<const u4*>(fimg + (half * 4 + r2) * 512);
+        him[half][r2] = *reinterpret_cast<const u4*>(fimg + 4096 + (half * 4 + r2) * 512);
+      }
+
+    // ---- pass 0: U / 4096 in fp32, times H' * 4096, one rounding, back into the image with the planes exchanged
+    transform(
+        [&](int k0, f4& o_re, f4& o_im) {
+#pragma unroll
+          for (int r2 = 0; r2 < 4; ++r2) {
+            const float fr = static_cast<float>(__builtin_bit_cast(h8, hre[k0 >> 3][r2])[k0 & 7]) * 4096.f;
+            const float fi = static_cast<float>(__builtin_bit_cast(h8, him[k0 >> 3][r2])[k0 & 7]) * 4096.f;
+            const float zr = __builtin_fmaf(o_re[r2], fr, -(o_im[r2] * fi));
+            o_im[r2] = __builtin_fmaf(o_re[r2], fi, o_im[r2] * fr);
+            o_re[r2] = zr;
+          }
+        },
+        [&](int half, int r2, u4 vr, u4 vi) {
+          // chunk c = 2 k1 + half + 32 k2 of a plane: block mm = c >> 6 = 2 g + (r2 >> 1), slot (c & 63) ^ 2 mm
+          const uint32_t mm = 2u * g + (r2 >> 1);
+          const uint32_t cl = 2u * (lane & 15) + half + 32u * (r2 & 1);
+          const uint32_t off = 1024u * mm + 16u * (cl ^ (2u * mm));
+          *reinterpret_cast<u4*>(wl + 8192 + off) = vr;
+          *reinterpret_cast<u4*>(wl + off) = vi;
+        });
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+    // the kept samples: window chunk j = 64 i + lane behind the halo, as long as its place in the sequence lies below L / 8
+    uint32_t pb, cb;
+    int32_t sb;
+    split_item(b, channels, geo, pb, sb, cb);
+    const bool has_im = 2 * pb + 1 < rows;
+    const int32_t first = sb * geo.hop - geo.halo;       // output chunk of window chunk 0
+    const uint64_t seq = static_cast<uint64_t>(2 * pb) * channels + cb;
+
+    // Post: the gate chunks of the RE plane's kept samples, issued here so that they fly under pass 1 (32 registers; the IM plane's
+    // as well would spill). The IM plane's are all issued behind pass 1, ahead of the RE plane's stores. Like the pre gate's, the
+    // loads sit under no per-lane branch: a lane that stores nothing reads output chunk s * hop / 8 of the same gate sequence, which
+    // this item always stores. The gate chunk is the OUTPUT chunk, not the window chunk.
+    const uint16_t* const g_re = post + seq * post_seq;                                                 // Post only
+    const uint16_t* const g_im = g_re + static_cast<uint64_t>(channels) * post_seq;
+    auto gate_off = [&](int i) {                                                                         // in halves, below 2^26
+      const int32_t j = 64 * i + lane;
+      const int32_t chunk = first + j;
+      return static_cast<uint32_t>(j >= geo.halo && chunk < geo.chunks ? chunk : sb * geo.hop) * 8u;
+    };
+    u4 gate[8], gate_im[8];
+    if constexpr (Post) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) gate[i] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(g_re + gate_off(i)));
+    }
+
+    // ---- pass 1: the inverse transform; staged through the image (slot swizzle of kStageOut), planes exchanged back
+    transform([](int, f4&, f4&) {},
+              [&](int half, int r2, u4 vr, u4 vi) {
+                const uint32_t slot = 2u * (lane & 15) + half;
+                const uint32_t off = 16u * (slot ^ ((slot >> 3) & 1)) + 512u * (4 * g + r2);
+                *reinterpret_cast<u4*>(wl + 8192 + off) = vr;
+                *reinterpret_cast<u4*>(wl + off) = vi;
+              });
+    uint16_t* const y_re = out + seq * out_seq;
+    uint16_t* const y_im = y_re + static_cast<uint64_t>(channels) * out_seq;
+    const uint32_t rd = 16u * (lane ^ ((lane >> 3) & 1));
+    if constexpr (Post) {
+      if (has_im) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) gate_im[i] = __builtin_nontemporal_load(reinterpret_cast<const u4*>(g_im + gate_off(i)));
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int32_t j = 64 * i + lane;
+        const int32_t chunk = first + j;
+        if (j >= geo.halo && chunk < geo.chunks) {
+          const u4 vr = mul8(*reinterpret_cast<const u4*>(wl + 1024 * i + rd), gate[i]);
+          st<kNonTemporal>(y_re + static_cast<int64_t>(chunk) * 8, vr);
+        }
+      }
+      if (has_im) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int32_t j = 64 * i + lane;
+          const int32_t chunk = first + j;
+          if (j >= geo.halo && chunk < geo.chunks) {
+            const u4 vi = mul8(*reinterpret_cast<const u4*>(wl + 8192 + 1024 * i + rd), gate_im[i]);
+            st<kNonTemporal>(y_im + static_cast<int64_t>(chunk) * 8, vi);
+          }
+        }
+      }
+    } else {
+      // sconv4096_kernel's store, statement by statement
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int32_t j = 64 * i + lane;
+        const int32_t chunk = first + j;
+        if (j >= geo.halo && chunk < geo.chunks) {
+          const int64_t half_off = static_cast<int64_t>(chunk) * 8;
+          const u4 vr = *reinterpret_cast<const u4*>(wl + 1024 * i + rd);
+          st<kNonTemporal>(y_re + half_off, vr);
+          if (has_im) {
+            const u4 vi = *reinterpret_cast<const u4*>(wl + 8192 + 1024 * i + rd);
+            st<kNonTemporal>(y_im + half_off, vi);
+          }
+        }
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // image read out before the next item's image is built
+    b += stride_b;
+  } while (b < items);
+}
+
+}  // namespace gsconv4096
