@@ -23,6 +23,9 @@ Eight layers, all thin:
 * :mod:`.gsconv` — ctypes binding of the gated overlap-save convolution add-on ``include/tfft_gsconv.h`` in ``libtfft_gsconv.so``
   (the gated operator of :mod:`.gconv` at any sequence length in one kernel; layered on ``libtfft_conv.so`` and ``libtfft.so``; no
   fallback).
+* :mod:`.gbconv` — ctypes binding of the gated gradient add-on ``include/tfft_gbconv.h`` in ``libtfft_gbconv.so`` (the gradients of
+  the gated overlap-save convolution, and the ``torch.autograd`` hook over them and :mod:`.gsconv`; layered on ``libtfft_conv.so``
+  and ``libtfft.so``; no fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -45,6 +48,9 @@ from .bconv import (TfftLongConvGradPlan, bconv_cache_clear, bconv_describe, bco
                     differentiable_long_causal_conv, load_bconv_library, long_causal_conv_input_grad, long_causal_conv_tap_grad)
 from .gsconv import (TfftGatedLongConvPlan, gated_long_causal_conv, gsconv_cache_clear, gsconv_describe, gsconv_geometry,  # noqa: F401
                      gsconv_lib_path, load_gsconv_library)
+from .gbconv import (TfftGatedLongConvGradPlan, differentiable_gated_long_causal_conv, gated_long_causal_conv_input_grad,  # noqa: F401
+                     gated_long_causal_conv_tap_grad, gbconv_cache_clear, gbconv_describe, gbconv_geometry, gbconv_lib_path,
+                     load_gbconv_library)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -70,6 +76,8 @@ __all__ = [
     "load_bconv_library", "long_causal_conv_input_grad", "long_causal_conv_tap_grad",
     "TfftGatedLongConvPlan", "gated_long_causal_conv", "gsconv_cache_clear", "gsconv_describe", "gsconv_geometry", "gsconv_lib_path",
     "load_gsconv_library",
+    "TfftGatedLongConvGradPlan", "differentiable_gated_long_causal_conv", "gated_long_causal_conv_input_grad",
+    "gated_long_causal_conv_tap_grad", "gbconv_cache_clear", "gbconv_describe", "gbconv_geometry", "gbconv_lib_path", "load_gbconv_library",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]
