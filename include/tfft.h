@@ -197,7 +197,18 @@ int tfft_plan_opts_known_size(size_t bytes);
  * commented-out variants (src/base/TensorFFT256.cu:163-177 "For unscaled results" / "For scaling in one step",
  * Radix2.cu:56-65). All three differ only by exact powers of two, so away from overflow / underflow they give the
  * same significands; what differs is the range of the fp16 intermediates:
- *   SEQUENTIAL  every radix-R stage divides by R: |intermediate| <= max|x| at every stage, no finite input overflows.
+ *   SEQUENTIAL  every radix-R stage divides by R: the complex MAGNITUDE of an intermediate is at most max |x_re + i x_im| (times
+ *               1 + 2^-11 per rounding of a constant or a stage). A single COMPONENT is not bounded by max|x|: a stage sums
+ *               rotated samples, and x_t = A (sgn cos + i sgn sin)(2 pi k t / N) puts 1.2568 A on one axis behind one radix-16
+ *               stage and 4/pi A into bin k. The intermediates are binary16 and nothing clamps them, so the input condition is
+ *                   |x_re + i x_im| <= 64512 for every sample (both components up to 45600 at once),
+ *               or, at N = 4096, a signal with an all-zero plane (a real signal), which may take any finite value (argued and
+ *               modelled for the three radix-16 stages of that length only; at other lengths a real signal beyond 64512 is
+ *               covered by nothing but the full-scale constant and alternating rows of the tests). 64512 = 63 * 2^10 leaves
+ *               room for 16 rounded stages (M (1 + 2^-11)^(2 S - 1) (1 + 2^-19)^S < 65520; the N = 4096 kernels have S = 3 and
+ *               stand 65359); tests/test_conv_range_host.py derives and models it. Beyond it the result may hold inf / nan:
+ *               the signal above at A = 65504 does (measured on the MI355X at N = 4096: 512, 32 and 1 of the
+ *               8192 output halves are inf or nan for k = 1, 16 and 256).
  *   NONE        no stage scales: result = DFT(x) (the cuFFT / hipFFT convention). fp16 intermediates grow by the
  *               radix per stage; nothing overflows as long as N * max|x| <= 65504 (worst case: a constant or a pure
  *               tone; white noise of rms s needs about 6 s sqrt(N) <= 65504). Beyond that the result holds inf / nan.

@@ -62,7 +62,8 @@
  * Range contract: that of tfft_sconv.h, per window. Input gradient: with G the unscaled spectrum of a window of the g pair,
  * max_k |G_k| |H_k| <= 32752 and max |window's circular correlation| <= 65504. Tap gradient: the "filter" is Zx's spectrum / 4096,
  * so max_k |G_k| |X_k| / 4096 <= 32752 and max |item's circular correlation| / 4096 <= 65504; for samples in (-1, 1) |X_k| / 4096
- * is about 0.03 and nothing comes near either bound.
+ * is about 0.03 and nothing comes near either bound. Every pair that is transformed (g in the input gradient, x and g in the tap
+ * gradient) has to meet |v_2p + i v_2p+1| <= 64512 sample by sample (tfft_sconv.h; a row without partner: any finite value).
  */
 #ifndef TFFT_BCONV_H_
 #define TFFT_BCONV_H_

@@ -35,11 +35,16 @@
  *       (256-byte aligned), call tfft_conv_plan_prepare() once, or let the first execution hipMalloc it. After either of the
  *       first two an execution only launches kernels. Executions of one such plan must not overlap in time.
  *
- * Range contract. The forward transform is sequentially scaled (1/R per radix-R stage: no finite input overflows in it). The
- * missing factor n is applied as an exact power of two to the fp32 filter value, the product with H is formed in fp32 and rounded
+ * Range contract. The forward transform is sequentially scaled (1/R per radix-R stage). That bounds the complex magnitude of its
+ * binary16 intermediates by that of the input, not each component (tfft.h, TFFT_SCALE_SEQUENTIAL), so the signal has to meet
+ *     |x_re + i x_im| <= 64512 for every sample (both components up to 45600 at once; any finite value where one plane is all zero).
+ * The missing factor n is applied as an exact power of two to the fp32 filter value, the product with H is formed in fp32 and rounded
  * ONCE to binary16, and the inverse transform is sequentially scaled again. Results are finite whenever
  *     max_k |X_k| |H_k| <= 32752   (X = the unscaled spectrum of the signal; half of 65504, so that either component fits)
- *     and max |y| <= 65504.
+ *     and max |y| <= 65504
+ * for such a signal. (Measured on the MI355X: x_t = 65504 (sgn cos + i sgn sin)(2 pi k t / 4096) with H = 2^-14 at every bin meets the
+ * last two conditions, max |X H| = 20 863 and max |y| = 5.7, and comes back as NaN in every sample for k = 1 and k = 16; k = 256 stays
+ * finite in the fused kernel, whose third stage is not rounded. At 45600 all three are finite and within 2 ulp of the exact answer.)
  * Fused path: the spectrum is never rounded to binary16 before the multiply (fp32 accumulators times H * 4096); composed path: the
  * forward plan's output X / n is binary16, the multiply is (X / n) * (H * n) in fp32.
  */

@@ -82,7 +82,8 @@
  * Range contract: that of tfft_bconv.h, per window, applied to the windows of gz and u and to H'. Input gradient: with G the
  * unscaled spectrum of a window of the gz pair, max_k |G_k| |H'_k| <= 32752, max |window's circular correlation| <= 65504, and
  * max |pre du|, max |x du| <= 65504. Tap gradient: max_k |G_k| |U_k| / 4096 <= 32752 and max |item's circular correlation| / 4096
- * <= 65504.
+ * <= 65504. Every pair that is transformed (gz in the input gradient, u and gz in the tap gradient: the gated values) has to meet
+ * |v_2p + i v_2p+1| <= 64512 sample by sample (tfft_bconv.h; a row without partner: any finite value).
  */
 #ifndef TFFT_GBCONV_H_
 #define TFFT_GBCONV_H_

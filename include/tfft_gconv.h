@@ -62,7 +62,8 @@
  *     max_k |U_k| |H'_k| <= 32752  (U = the unscaled n-point spectrum of the zero-padded pair u_2p + i u_2p+1)
  *     and max |z| <= 65504         (z = the full linear convolution of the pair with the skip-carrying taps, discarded samples
  *                                   included)
- *     and max |g z| <= 65504.
+ *     and max |g z| <= 65504
+ *     and |u_2p + i u_2p+1| <= 64512 for every sample of a pair of rows (tfft_lconv.h: the condition is on the gated input).
  */
 #ifndef TFFT_GCONV_H_
 #define TFFT_GCONV_H_

@@ -65,7 +65,8 @@
  * spectrum of one window of the pair u_2p + i u_2p+1, results are finite whenever
  *     max_k |U_k| |H'_k| <= 32752
  *     and max |z| <= 65504     (z = the window's full 4096-point circular convolution, the discarded halo included)
- *     and max |g z| <= 65504.
+ *     and max |g z| <= 65504
+ *     and |u_2p + i u_2p+1| <= 64512 for every sample of a pair of rows (tfft_sconv.h: the condition is on the gated input).
  */
 #ifndef TFFT_GSCONV_H_
 #define TFFT_GSCONV_H_

@@ -42,8 +42,11 @@
  *       aligned), call tfft_lconv_plan_prepare() once, or let the first execution hipMalloc it. After either of the first two an
  *       execution only launches kernels. Executions of one such plan must not overlap in time.
  *
- * Range contract: that of tfft_conv.h. The forward transform is sequentially scaled (no finite input overflows in it), the
- * missing factor n is applied as an exact power of two to the fp32 filter value, the product with H is formed in fp32 and
+ * Range contract: that of tfft_conv.h. The forward transform is sequentially scaled, which bounds the complex magnitude of its
+ * intermediates, not each component: rows 2p and 2p + 1 of a channel travel as one complex signal, so the PAIR has to meet
+ *     |x_2p + i x_2p+1| <= 64512 for every sample (both rows up to 45600 at once); the last row of an odd count, whose partner is
+ *     zero, may take any finite value.
+ * The missing factor n is applied as an exact power of two to the fp32 filter value, the product with H is formed in fp32 and
  * rounded ONCE to binary16, and the inverse transform is sequentially scaled again. Results are finite whenever
  *     max_k |X_k| |H_k| <= 32752   (X = the unscaled n-point spectrum of the zero-padded pair x_2p + i x_2p+1)
  *     and max |y| <= 65504         (y = the full linear convolution of the pair, discarded samples included).

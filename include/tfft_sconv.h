@@ -52,7 +52,8 @@
  * Range contract: that of tfft_lconv.h, per window. With X = the unscaled 4096-point spectrum of one window of the pair
  * x_2p + i x_2p+1, results are finite whenever
  *     max_k |X_k| |H_k| <= 32752
- *     and max |y| <= 65504     (y = the window's full 4096-point circular convolution, the discarded halo included).
+ *     and max |y| <= 65504     (y = the window's full 4096-point circular convolution, the discarded halo included)
+ *     and |x_2p + i x_2p+1| <= 64512 for every sample of a pair of rows (both up to 45600 at once; a row without partner: any finite value).
  */
 #ifndef TFFT_SCONV_H_
 #define TFFT_SCONV_H_

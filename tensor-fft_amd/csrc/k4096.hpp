@@ -38,9 +38,11 @@
 //   VGPR -> HBM   each lane ends up with 16 consecutive outputs (k0 = 0..15) for
 //                 4 values of k2: 32-byte runs, stored as 16-byte vectors.
 //
-// Scaling: 1/16 per stage folded into F, G, H (exact in binary16), so every
-// intermediate is bounded by max|x| and nothing is pushed into the subnormal
-// range the way the reference's up-front x/4096 is (TensorFFT4096.cu:169-173).
+// Scaling: 1/16 per stage folded into F, G, H (exact in binary16), so the complex
+// magnitude of every intermediate is bounded by that of the input (one component
+// is not: include/tfft.h, TFFT_SCALE_SEQUENTIAL) and nothing is pushed into the
+// subnormal range the way the reference's up-front x/4096 is
+// (TensorFFT4096.cu:169-173).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -10,6 +10,13 @@ for the same reason: an inverse transform spreads the spectrum's rounding over s
                      filter, gauss), rel-L2 6.4e-4; 1.5 x 2.102 = 3.15 -> 3.5
     K_CONV_COMPOSED  forward plan, cmul, inverse plan (spectrum rounded, multiplied, rounded again): class worst 2.560 ulp (2^20), rel-L2
                      8.2e-4; 1.5 x 2.560 = 3.84 -> 4.0
+
+Both hold unchanged at the upper edge of the range contract (profiles/range_ulps.txt, tests/test_gpu_conv_range.py: signals, filters
+or both scaled until max |X H| lies within a factor 2 of 32752). They are constants for signals whose peak is 2 to 3 x their rms, as
+the profile's are. One input outside that class is known: a REAL full-scale square wave of one period, +-65504 at every sample, times
+H = 2^-14 comes back 4.000 ulp from the exact answer through conv4096's arithmetic (measured through sconv4096_kernel, which restates
+it bit for bit and is held to K_SCONV = 4.0 there; tests/test_conv_range_host.py reproduces the 4.0 from the six roundings in numpy):
+every sample is at the peak, the peak at the top of a binade, and the roundings of the one dominant tone add up.
 """
 import numpy as np
 
@@ -88,3 +95,11 @@ def reference(x_re, x_im, h_re, h_im, index=None):
 def signals(n, batch, rng):
     """uniform(-1, 1) binary16, different for every signal"""
     return rng.uniform(-1, 1, (batch, n)).astype(np.float16), rng.uniform(-1, 1, (batch, n)).astype(np.float16)
+
+
+def case_data(n, batch, filters, kind, seed):
+    """(x_re, x_im, h_re, h_im) of a case: the signals above and the binary16 planes of make_filters"""
+    rng = np.random.default_rng([seed, n, batch, filters, FILTER_KINDS.index(kind)])
+    x_re, x_im = signals(n, batch, rng)
+    h_re, h_im = to_half_planes(make_filters(kind, n, filters, rng))
+    return x_re, x_im, h_re, h_im

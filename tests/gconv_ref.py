@@ -100,15 +100,16 @@ def reference_true(u, h, skip, n):
     return lr._convolve(u, np.fft.fft(taps_with_skip(h, skip), n, axis=-1), n)
 
 
-def delay_expected(u, h_channels_taps, skip, g):
-    """the exact answer of the delay kind: g (.) (shift(u) + d u) in fp64, [B][C][L]"""
+def delay_expected(u, h_channels_taps, skip, g, tap=None):
+    """the exact answer of the delay kind: g (.) (shift(u) + d u) in fp64, [B][C][L]; tap: the value of the one tap of every channel
+    [C], 1 where it is not given"""
     rows, channels, length = u.shape
     taps = h_channels_taps
     out = np.zeros(u.shape)
     for c in range(channels):
         d = lr.delay_shift(c, taps)
         if d < length:
-            out[:, c, d:] = u[:, c, :length - d].astype(np.float64)
+            out[:, c, d:] = (1.0 if tap is None else float(tap[c])) * u[:, c, :length - d].astype(np.float64)
         if skip is not None:
             out[:, c] += float(skip[c]) * u[:, c].astype(np.float64)
     return out if g is None else g.astype(np.float64) * out

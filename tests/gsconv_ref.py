@@ -80,9 +80,9 @@ def post_gate_tolerance(y, g, k, peak, rows, channels, length, taps):
             + 0.5 * eb.ulp16(np.abs(y.astype(np.float64))))
 
 
-def delay_expected(u, taps, skip, g):
+def delay_expected(u, taps, skip, g, tap=None):
     """the exact answer of the delay kind: g (.) (shift(u) + d u) in fp64, [B][C][L]"""
-    return gr.delay_expected(u, taps, skip, g)
+    return gr.delay_expected(u, taps, skip, g, tap)
 
 
 def model(x, h, p, g, skip):

@@ -20,6 +20,9 @@ against fp64 with the plan's own binary16 spectrum, and K = the smallest half-in
               has 2^-10; 3.000 x 2^-11 is 1.5 ulp of a pair. The causal plans' zero partners have half-empty windows and the
               convolution plans' profile has no real signal, so neither profile met it. 1.5 x 3.000 = 4.5 exceeds the ceiling, so
               K_SCONV is the ceiling, 4.0, as K_REAL is (tests/elementwise_bound.py); DESIGN.md 3.11.
+              At the upper edge of the range contract the classes do not move (profiles/range_ulps.txt). One zero-partner input
+              reaches the constant exactly: the lone row +-65504 of one period with the tap 2^-14, 4.000 ulp
+              (tests/test_gpu_conv_range.py::test_corner_signal_overlap_save, explained there and modelled on the CPU).
               rel-L2 of the kept samples of a window: at most 6.5e-4 everywhere but box taps at K = 2049, 1.08e-3 to 1.69e-3 (seed 2;
               the running mean of 2049 samples, an output of about 1/45 of the input's size; profiles/lconv_ulps.txt shows the same
               taps at 1.08e-3 to 1.17e-3 on half-empty windows). The test's seed stays under elementwise_bound.REL_L2.

@@ -84,14 +84,13 @@ def run_conv(tf, n, batch, filters, composed, x_re, x_im, h_re, h_im, in_place=F
 
 
 def _case_data(n, batch, filters, kind, seed):
-    rng = np.random.default_rng([seed, n, batch, filters, conv_ref.FILTER_KINDS.index(kind)])
-    x_re, x_im = conv_ref.signals(n, batch, rng)
-    h_re, h_im = conv_ref.to_half_planes(conv_ref.make_filters(kind, n, filters, rng))
-    return x_re, x_im, h_re, h_im
+    return conv_ref.case_data(n, batch, filters, kind, seed)
 
 
-def _check_case(tf, n, batch, filters, composed, kind, seed=1):
-    x_re, x_im, h_re, h_im = _case_data(n, batch, filters, kind, seed)
+def _check_case(tf, n, batch, filters, composed, kind, seed=1, data=None, exact_filter=True):
+    """data: (x_re, x_im, h_re, h_im) in place of the case's own (tests/test_gpu_conv_range.py: the same case at another amplitude);
+    exact_filter = False: the delay filters were rounded again, the comparison with numpy.roll is left out"""
+    x_re, x_im, h_re, h_im = _case_data(n, batch, filters, kind, seed) if data is None else data
     y_re, y_im = run_conv(tf, n, batch, filters, composed, x_re, x_im, h_re, h_im)
     r_re, r_im = conv_ref.reference(x_re, x_im, h_re, h_im)
     k = conv_ref.K_CONV_COMPOSED if composed or n != 4096 else conv_ref.K_CONV_FUSED
@@ -101,11 +100,12 @@ def _check_case(tf, n, batch, filters, composed, kind, seed=1):
     if kind == "ones":
         # y = x up to the arithmetic: the same bound against the input itself
         eb.check(y_re, y_im, x_re.astype(np.float64), x_im.astype(np.float64), k, what=what + " (y = x)")
-    if kind == "delays":
-        # a wrong filter index or bin map is a wrong roll
+    if kind == "delays" and exact_filter:
+        # a wrong filter index or bin map is a wrong roll (times the filter's gain H_0: 1 in this file's cases)
         idx = np.arange(batch) % filters
-        want_re = np.stack([np.roll(x_re[b].astype(np.float64), conv_ref.delay_shift(idx[b], n)) for b in range(batch)])
-        want_im = np.stack([np.roll(x_im[b].astype(np.float64), conv_ref.delay_shift(idx[b], n)) for b in range(batch)])
+        gain = h_re[:, 0].astype(np.float64)
+        want_re = np.stack([gain[idx[b]] * np.roll(x_re[b].astype(np.float64), conv_ref.delay_shift(idx[b], n)) for b in range(batch)])
+        want_im = np.stack([gain[idx[b]] * np.roll(x_im[b].astype(np.float64), conv_ref.delay_shift(idx[b], n)) for b in range(batch)])
         # The binary16 filter is not an exact delay: each component of H_k is rounded to 11 bits, |dH_k| <= 2^-11 |H_k|, rms about
         # 0.4 x that. The inverse transform spreads it over the samples: rel-L2 <= 2^-11 on top of the arithmetic, and per sample
         # sigma = 0.4 * 2^-11 * rms(y) = 0.12 ulp of a peak of 1.41 (y is x rolled: components of rms 0.58), 4.5 sigma over the
@@ -194,6 +194,13 @@ def test_composed_is_forward_cmul_inverse_bit_for_bit(tf, n, batch, filters):
     the plans where the length has one, the filter permuted by tfft_conv_filter_slot)."""
     x_re, x_im, h_re, h_im = _case_data(n, batch, filters, "decay", 4)
     got_re, got_im = run_conv(tf, n, batch, filters, True, x_re, x_im, h_re, h_im, pad=False)
+    w_re, w_im = forward_cmul_inverse(tf, n, batch, filters, x_re, x_im, h_re, h_im)
+    assert np.array_equal(got_re.view(np.uint16), w_re.view(np.uint16)) and np.array_equal(got_im.view(np.uint16), w_im.view(np.uint16))
+
+
+def forward_cmul_inverse(tf, n, batch, filters, x_re, x_im, h_re, h_im):
+    """the composed path by its parts: the library's forward plan, conv_ref.cmul on the host, the library's inverse plan: the fp16
+    planes [batch][n]"""
     order = "transposed" if tf.transposed_n2(n) else "natural"
     fwd = tf.TfftPlan(n, batch, 0, preserve_input=True, output_order=order)
     inv = tf.TfftPlan(n, batch, 0, input_order=order)
@@ -211,8 +218,7 @@ def test_composed_is_forward_cmul_inverse_bit_for_bit(tf, n, batch, filters):
     d_y = torch.empty_like(d_z)
     inv.exec_inverse(d_z, d_z[n:], d_y, d_y[n:])
     torch.cuda.synchronize()
-    w_re, w_im = _unblock(d_y.cpu().numpy(), batch, n, 2 * n)
-    assert np.array_equal(got_re.view(np.uint16), w_re.view(np.uint16)) and np.array_equal(got_im.view(np.uint16), w_im.view(np.uint16))
+    return _unblock(d_y.cpu().numpy(), batch, n, 2 * n)
 
 
 def test_filter_can_be_replaced_and_exec_needs_one(tf):

@@ -163,8 +163,11 @@ def _differs(y, want, what, yardstick):
     return f"{what}: differs from {yardstick} in {len(bad)} samples, first (b, c, t) = {bad[:3].tolist()}"
 
 
-def check_case(tf, length, taps, rows, channels, kind, mode, k, launch_iters=0, composed=False, seed=1):
-    x, h, p, g, skip = gr.case_data(length, taps, rows, channels, kind, seed, mode)
+def check_case(tf, length, taps, rows, channels, kind, mode, k, launch_iters=0, composed=False, seed=1, data=None, exact_taps=True):
+    """data: (x, h, p, g, skip) in place of the case's own (tests/test_gpu_conv_range.py: the same case at another amplitude);
+    exact_taps = False: the taps were rounded again, so comparison 3 and the shifted input are left out. Returns the worst error of
+    z = the shipped plan's result with this plan's spectrum (yardstick 2: y is g (.) z bit for bit) against fp64 with that spectrum."""
+    x, h, p, g, skip = gr.case_data(length, taps, rows, channels, kind, seed, mode) if data is None else data
     n = gr.plan_length(length, taps, composed)
     path = "fused" if n == 4096 and not composed else "composed"
     what = f"gconv L={length} K={taps} B={rows} C={channels} iters={launch_iters} {path} {kind} {mode}"
@@ -181,21 +184,29 @@ def check_case(tf, length, taps, rows, channels, kind, mode, k, launch_iters=0, 
     true = gr.reference_true(u, h, skip, n)
     peak = lr.pair_peak(true)
     # 3. truth, where no second gate rounds the result again
-    if g is None:
+    if g is None and exact_taps:
         got_re, got_im = lr.pair_planes(y.astype(np.float64), length)
         if rows % 2:
             true[-channels:].imag = 0.0             # the zero partner has no output: zeros on both sides
         worst = eb.check(got_re, got_im, true.real[:, :length], true.imag[:, :length], k + 1.0, rel_l2=eb.REL_L2 + 2.0 ** -11, peak=peak,
                          what=what + " (true linear convolution with skip)")
         print(f"{what}: worst {worst:.3f} ulp against the truth")
-    if kind == "delay":
+    if kind == "delay" and exact_taps:
         # a wrong filter index is a wrong delay: the exact answer in front of the post gate is the gated input shifted, plus d u,
         # under the bound of tests/test_gpu_lconv.py. Without a post gate that is y itself. With one, y has just been shown to be
         # g (.) z bit for bit, z the shipped plan's result with this plan's spectrum, so the check is made on that z: the gate's own
         # rounding needs no allowance, and a wrong gate index cannot pass yardstick 2.
-        expected = gr.delay_expected(u, taps, skip, None)
+        expected = gr.delay_expected(u, taps, skip, None, tap=[h[c, lr.delay_shift(c, taps)] for c in range(channels)])
         before_gate = y if g is None else z
         assert np.abs(before_gate.astype(np.float64) - expected).max() <= (k + 1.0) * eb.ulp16(peak.max()), what
+    # what the amplitude tests and tools/range_accuracy.py record: z against fp64 with the plan's own spectrum, in the pair's unit
+    ref = lr.reference_spectrum(u, spec[0], spec[1], n)[:, :length]
+    if rows % 2:
+        ref[-channels:].imag = 0.0
+    z_re, z_im = lr.pair_planes(z.astype(np.float64), length)
+    if data is not None:
+        return eb.check(z_re, z_im, ref.real, ref.imag, k, peak=peak, what=what + " (z against fp64 with the plan's spectrum)")
+    return float(eb.errors_in_ulps(z_re, z_im, ref.real, ref.imag, peak=peak).max())
 
 
 @pytest.mark.parametrize("mode", list(gr.GATE_MODES))

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import elementwise_bound as eb
+import range_ref
 from tensor_fft_amd import capi
 
 K_ANY = max(eb.K_TABLE, eb.K_SINCOS)        # per-element bound of a plan that may take either twiddle source
@@ -168,8 +169,9 @@ def test_n4096_golden_benchmark_signal(tf, torch, orc, golden_dir):
 
 
 def test_n4096_large_and_tiny_magnitudes(tf, torch, orc):
-    """Per-stage 1/16 scaling keeps |intermediates| <= max|x|: no overflow at fp16 max, and small inputs
-    are not flushed the way an up-front x/4096 (TensorFFT4096.cu:169-173) pushes them into subnormals."""
+    """Per-stage 1/16 scaling keeps the complex magnitude of the intermediates at that of the input (not each component:
+    test_full_scale_inputs_do_not_overflow), so noise of amplitude 60000, whose stage means stay far below it, does not overflow,
+    and small inputs are not flushed the way an up-front x/4096 (TensorFFT4096.cu:169-173) pushes them into subnormals."""
     rng = np.random.default_rng(9)
     base = rng.uniform(-1, 1, (2, 2, 4096))
     re = np.stack([base[0, 0] * 60000, base[1, 0] * 2e-3]).astype(np.float16)
@@ -185,16 +187,25 @@ def test_n4096_large_and_tiny_magnitudes(tf, torch, orc):
 
 @pytest.mark.parametrize("n", [256, 512, 1024, 2048, 4096, 8192, 16384, 32768, 65536])
 def test_full_scale_inputs_do_not_overflow(tf, torch, orc, n):
-    """Every kernel family scales by its radix per stage, so |intermediates| <= max|x|: full-scale constant and
-    alternating inputs (fp16 max = 65504) give the exact DC / Nyquist line, full-scale noise stays finite."""
+    """Every kernel family scales by its radix per stage, so the complex MAGNITUDE of an intermediate is at most that of the input
+    (times 1 + 2^-11 per rounding): full-scale constant and alternating inputs (fp16 max = 65504) give the exact DC / Nyquist line,
+    full-scale noise stays finite. A single COMPONENT is not bounded that way: a stage sums rotated samples, and
+    A (sgn cos + i sgn sin) puts 1.2568 A on one axis (include/tfft.h, TFFT_SCALE_SEQUENTIAL; derived and modelled in
+    tests/test_conv_range_host.py). The contract is |x_re + i x_im| <= 64512 for samples with both planes in use: row 3 (n = 4096)
+    is that signal at the bound, both components 45600, turning once per 16 samples of stride 16, where the second stage's twiddle
+    adds to the sum: a component of 1.2813 x 45600 = 58 429 behind that stage, 4 / pi x 45600 = 58 060 in bin 16. Rows 0 and 2 have larger magnitudes and are fine for their own reasons:
+    a constant is not rotated at all, and a mean of 16 independent samples stays far below the worst case."""
     rng = np.random.default_rng(n)
-    re = np.empty((3, n), np.float16)
-    im = np.empty((3, n), np.float16)
+    rows = 4 if n == 4096 else 3
+    re = np.empty((rows, n), np.float16)
+    im = np.empty((rows, n), np.float16)
     re[0], im[0] = 65504.0, -65504.0
     re[1] = 65504.0 * (1 - 2 * (np.arange(n) & 1))
     im[1] = 0.0
     re[2] = (rng.uniform(-1, 1, n) * 65504).astype(np.float16)
     im[2] = (rng.uniform(-1, 1, n) * 65504).astype(np.float16)
+    if n == 4096:
+        re[3], im[3] = range_ref.corner_signals(range_ref.A_PAIR, 16)
     gr, gi = _run(tf, torch, re, im)
     got = _c(gr, gi)
     assert np.isfinite(got).all()
@@ -204,6 +215,10 @@ def test_full_scale_inputs_do_not_overflow(tf, torch, orc, n):
     assert np.abs(got[1] - want1).max() <= 65504 * 2.0 ** -10
     exact = _c(*orc.dft64(re[2:], im[2:]))
     assert np.linalg.norm(got[2] - exact[0]) / np.linalg.norm(exact[0]) < REL_L2_TOL
+    if n == 4096:
+        # the fundamental, bin 16 at 4 / pi A, carries 0.81 of the energy; every bin within K_TABLE ulps of it
+        assert abs(abs(exact[1][16]) / 45600.0 - 4 / np.pi) < 1e-3
+        eb.check(got[3].real, got[3].imag, exact[1].real, exact[1].imag, eb.K_TABLE, what="corner signal at the bound")
 
 
 @pytest.mark.parametrize("n", [256, 512, 2048, 8192, 32768, 65536])
