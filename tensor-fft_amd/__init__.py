@@ -3,7 +3,7 @@
 Import name: ``tensor_fft_amd`` (see ``tensor_fft_amd.py`` at the repository
 root; the directory carries the upstream project's hyphen).
 
-Eight layers, all thin:
+Nine layers, all thin:
 
 * :mod:`.capi` — ctypes binding of the C ABI ``include/tfft.h`` in
   ``libtfft.so`` (hand-written HIP, built in-tree by ``__graft_entry__.build``).
@@ -26,6 +26,9 @@ Eight layers, all thin:
 * :mod:`.gbconv` — ctypes binding of the gated gradient add-on ``include/tfft_gbconv.h`` in ``libtfft_gbconv.so`` (the gradients of
   the gated overlap-save convolution, and the ``torch.autograd`` hook over them and :mod:`.gsconv`; layered on ``libtfft_conv.so``
   and ``libtfft.so``; no fallback).
+* :mod:`.cconv` — ctypes binding of the carried convolution add-on ``include/tfft_cconv.h`` in ``libtfft_cconv.so`` (the plans of
+  :mod:`.sconv` and :mod:`.bconv` on a chunk of a longer sequence, with the history in front of x and the future behind g read in
+  place, and the ``torch.autograd`` hook over them; layered on ``libtfft_conv.so`` and ``libtfft.so``; no fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -51,6 +54,9 @@ from .gsconv import (TfftGatedLongConvPlan, gated_long_causal_conv, gsconv_cache
 from .gbconv import (TfftGatedLongConvGradPlan, differentiable_gated_long_causal_conv, gated_long_causal_conv_input_grad,  # noqa: F401
                      gated_long_causal_conv_tap_grad, gbconv_cache_clear, gbconv_describe, gbconv_geometry, gbconv_lib_path,
                      load_gbconv_library)
+from .cconv import (TfftChunkedConvGradPlan, TfftChunkedConvPlan, cconv_cache_clear, cconv_describe, cconv_geometry, cconv_lib_path,  # noqa: F401
+                    chunked_causal_conv, chunked_causal_conv_input_grad, chunked_causal_conv_tap_grad,
+                    differentiable_chunked_causal_conv, load_cconv_library, next_history)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -78,6 +84,9 @@ __all__ = [
     "load_gsconv_library",
     "TfftGatedLongConvGradPlan", "differentiable_gated_long_causal_conv", "gated_long_causal_conv_input_grad",
     "gated_long_causal_conv_tap_grad", "gbconv_cache_clear", "gbconv_describe", "gbconv_geometry", "gbconv_lib_path", "load_gbconv_library",
+    "TfftChunkedConvGradPlan", "TfftChunkedConvPlan", "cconv_cache_clear", "cconv_describe", "cconv_geometry", "cconv_lib_path",
+    "chunked_causal_conv", "chunked_causal_conv_input_grad", "chunked_causal_conv_tap_grad", "differentiable_chunked_causal_conv",
+    "load_cconv_library", "next_history",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]
