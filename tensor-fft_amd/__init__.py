@@ -57,6 +57,9 @@ from .gbconv import (TfftGatedLongConvGradPlan, differentiable_gated_long_causal
 from .cconv import (TfftChunkedConvGradPlan, TfftChunkedConvPlan, cconv_cache_clear, cconv_describe, cconv_geometry, cconv_lib_path,  # noqa: F401
                     chunked_causal_conv, chunked_causal_conv_input_grad, chunked_causal_conv_tap_grad,
                     differentiable_chunked_causal_conv, load_cconv_library, next_history)
+from .gcconv import (TfftGatedChunkedConvGradPlan, TfftGatedChunkedConvPlan, differentiable_gated_chunked_causal_conv,  # noqa: F401
+                     gated_chunked_causal_conv, gated_chunked_causal_conv_input_grad, gated_chunked_causal_conv_tap_grad,
+                     gcconv_cache_clear, gcconv_describe, gcconv_geometry, gcconv_lib_path, load_gcconv_library)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -87,6 +90,9 @@ __all__ = [
     "TfftChunkedConvGradPlan", "TfftChunkedConvPlan", "cconv_cache_clear", "cconv_describe", "cconv_geometry", "cconv_lib_path",
     "chunked_causal_conv", "chunked_causal_conv_input_grad", "chunked_causal_conv_tap_grad", "differentiable_chunked_causal_conv",
     "load_cconv_library", "next_history",
+    "TfftGatedChunkedConvGradPlan", "TfftGatedChunkedConvPlan", "differentiable_gated_chunked_causal_conv", "gated_chunked_causal_conv",
+    "gated_chunked_causal_conv_input_grad", "gated_chunked_causal_conv_tap_grad", "gcconv_cache_clear", "gcconv_describe", "gcconv_geometry",
+    "gcconv_lib_path", "load_gcconv_library",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]
