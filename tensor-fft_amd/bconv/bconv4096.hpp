@@ -30,15 +30,6 @@ using k4096::s4;
 using k4096::u2;
 using k4096::u4;
 
-// slot of bin k in a plane of the filter image: conv4096::filter_slot restated, as sconv4096.hpp restates it.
-// tests/test_gpu_bconv.py holds it to the shipped kernel: that kernel, given the natural-order conjugated spectrum and windows
-// built on the host, must reproduce dgrad_kernel's output bit for bit.
-__host__ __device__ constexpr uint32_t filter_slot(uint32_t k) {
-  const uint32_t k0 = k & 15, k1 = (k >> 4) & 15, k2 = k >> 8;
-  const uint32_t half = k0 >> 3, j = k0 & 7, g = k2 >> 2, r2 = k2 & 3;
-  return ((half * 4 + r2) * 64 + 16 * g + k1) * 8 + j;
-}
-
 // one plane's share of a 1-KiB block by LDS-DMA, nt: sconv4096::dma_chunk
 __device__ __forceinline__ void dma_chunk(const uint8_t* src, uint32_t dst) {
   uint32_t keep;

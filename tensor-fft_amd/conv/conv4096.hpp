@@ -28,13 +28,6 @@ using k4096::s4;
 using k4096::u2;
 using k4096::u4;
 
-// slot of bin k in a plane of the fused filter image (see above); a bijection of 0 .. 4095
-__host__ __device__ constexpr uint32_t filter_slot(uint32_t k) {
-  const uint32_t k0 = k & 15, k1 = (k >> 4) & 15, k2 = k >> 8;
-  const uint32_t half = k0 >> 3, j = k0 & 7, g = k2 >> 2, r2 = k2 & 3;
-  return ((half * 4 + r2) * 64 + 16 * g + k1) * 8 + j;
-}
-
 // in_* / out_*: planar binary16, signal b at + b * stride halves. tables: the first k4096::kOffF1n bytes of a
 // k4096::build_tables() blob (default scaling). filt: filter images, filter f at + f * 8192 halves; signal b takes b % filters.
 __global__ __launch_bounds__(k4096::kThreads, 2) void conv4096_kernel(

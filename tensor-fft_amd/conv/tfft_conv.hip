@@ -2,55 +2,14 @@
 //
 // Layered on libtfft.so through include/tfft.h only (sub-plans of the composed path, tfft_device_check, tfft_abi_version); from
 // csrc/ it takes k4096.hpp, header only, for the device helpers and the constant tables of the fused kernel (the add-on
-// uploads a copy of its own).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstring>
-#include <mutex>
-#include <string>
-#include <vector>
-
+// uploads a copy of its own). The error plumbing, the ABI check, the overlap test, filter_slot and the launch shape are those of
+// host_math.hpp and host_plumbing.hpp beside this file, the two headers every convolution library includes.
 #include "../../include/tfft_conv.h"
 #include "cmul.hpp"
 #include "conv4096.hpp"
+#include "host_plumbing.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-int hip_fail(hipError_t e, const char* what) { return fail(TFFT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-// a failing call into libtfft.so: its message becomes ours
-int pass_through(int rc) {
-  if (rc != TFFT_OK) g_err = tfft_last_error();
-  return rc;
-}
-#define CONV_HIP(call)                        \
-  do {                                        \
-    const hipError_t e_ = (call);             \
-    if (e_ != hipSuccess) return hip_fail(e_, #call); \
-  } while (0)
-
-inline bool is_pow2(uint64_t v) { return v && !(v & (v - 1)); }
-inline int ilog2(uint64_t v) {
-  int l = 0;
-  while (v >>= 1) ++l;
-  return l;
-}
-
-constexpr uint64_t kMinN = 256, kMaxN = uint64_t{1} << 26;
-
-int check_abi() {
-  static const int version = tfft_abi_version();
-  if (version != TFFT_ABI_VERSION)
-    return fail(TFFT_ERR_ARG, "libtfft.so speaks ABI " + std::to_string(version) + ", libtfft_conv.so was built against ABI " +
-                                  std::to_string(TFFT_ABI_VERSION) + ": rebuild the add-on");
-  return TFFT_OK;
-}
 
 int check_shape(uint64_t n, uint64_t batch, uint64_t filters, int flags) {
   if (!is_pow2(n)) return fail(TFFT_ERR_ARG, "n must be a power of two");
@@ -70,24 +29,12 @@ inline bool fused_shape(uint64_t n, int flags) { return n == 4096 && !(flags & T
 
 // slot of bin k in a plane of the filter image (include/tfft_conv.h)
 uint64_t filter_slot(uint64_t n, int flags, uint64_t k) {
-  if (fused_shape(n, flags)) return conv4096::filter_slot(static_cast<uint32_t>(k));
+  if (fused_shape(n, flags)) return host_math::filter_slot(static_cast<uint32_t>(k));
   const uint64_t n2 = tfft_plan_transposed_n2(n);
   if (!n2) return k;
   const uint64_t n1 = n / n2;
   return (k % n1) * n2 + k / n1;
 }
-
-// Element-exact test whether two planes (batch blocks of n halves, `stride` halves apart) share a half: the test of tfft_exec.
-bool planes_overlap(const void* pa, uint64_t sa, const void* pb, uint64_t sb, uint64_t batch, uint64_t n) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(pa), b = reinterpret_cast<uintptr_t>(pb);
-  const uintptr_t a_end = a + 2 * ((batch - 1) * sa + n), b_end = b + 2 * ((batch - 1) * sb + n);
-  if (a_end <= b || b_end <= a) return false;
-  if (batch == 1 || sa != sb) return true;            // different strides: conservative
-  const uint64_t d = static_cast<uint64_t>(a > b ? a - b : b - a) / 2 % sa;
-  return d < n || sa - d < n;
-}
-
-inline size_t round256(size_t v) { return (v + 255) & ~size_t{255}; }
 
 // The transform chain tfft_plan_create gives a plan of this shape, in the words of tfft_plan_describe. tfft.h has no describe call
 // for the transposed orders, so their two sub-plans (tfft.hip, create_transposed / create_transposed_in) are described one by one;
@@ -97,13 +44,13 @@ int describe_chain(uint64_t n, uint64_t batch, bool inverse, std::string& out) {
   const uint64_t n2 = tfft_plan_transposed_n2(n);
   if (!n2) {
     // (the planner bits a variant-0 plan of this batch gets: small batches take other splits)
-    const int rc = pass_through(tfft_plan_describe(n, 1, tfft_plan_default_variant(n, 1, batch), a, sizeof(a)));
+    const int rc = pass_tfft(tfft_plan_describe(n, 1, tfft_plan_default_variant(n, 1, batch), a, sizeof(a)));
     out = a;
     return rc;
   }
   const uint64_t n1 = n / n2;
-  int rc = pass_through(tfft_plan_describe(n1, n2, n1 == 512 ? TFFT_VARIANT_RADIX512_ONE_PASS : 0, a, sizeof(a)));
-  if (rc == TFFT_OK) rc = pass_through(tfft_plan_describe(n2, 1, 0, b, sizeof(b)));
+  int rc = pass_tfft(tfft_plan_describe(n1, n2, n1 == 512 ? TFFT_VARIANT_RADIX512_ONE_PASS : 0, a, sizeof(a)));
+  if (rc == TFFT_OK) rc = pass_tfft(tfft_plan_describe(n2, 1, 0, b, sizeof(b)));
   if (rc) return rc;
   out = inverse ? std::string(b) + " " + a : std::string(a) + " " + b;      // transposed input: rows first, then the column pass
   return TFFT_OK;
@@ -133,8 +80,8 @@ namespace {
 int bind_workspace(const tfft_conv_plan* p) {
   if (!p->sub_bytes) return TFFT_OK;
   void* sub = static_cast<uint8_t*>(p->ws) + p->spec_bytes;
-  int rc = pass_through(tfft_plan_set_workspace(p->fwd, tfft_plan_workspace_bytes(p->fwd) ? sub : nullptr, p->sub_bytes));
-  if (rc == TFFT_OK) rc = pass_through(tfft_plan_set_workspace(p->inv, tfft_plan_workspace_bytes(p->inv) ? sub : nullptr, p->sub_bytes));
+  int rc = pass_tfft(tfft_plan_set_workspace(p->fwd, tfft_plan_workspace_bytes(p->fwd) ? sub : nullptr, p->sub_bytes));
+  if (rc == TFFT_OK) rc = pass_tfft(tfft_plan_set_workspace(p->inv, tfft_plan_workspace_bytes(p->inv) ? sub : nullptr, p->sub_bytes));
   return rc;
 }
 
@@ -148,22 +95,6 @@ int ensure_workspace(const tfft_conv_plan* p) {
   p->ws_bytes = need;
   p->ws_owned = true;
   return bind_workspace(p);
-}
-
-// launch shape of the fused kernel: that of fft4096_kernel<kStageOut | kNonTemporal> (tfft.hip, live_waves / k4096_shape): one
-// wave per SIMD on as many CUs as there are for a batch that does not fill the chip, else 8 waves per workgroup; about two
-// signals per wave and the hardware dispatcher handing out workgroups as CUs drain once the batch is four chips' worth.
-void conv4096_shape(const tfft_conv_plan* p, uint32_t& live, uint32_t& grid) {
-  const uint64_t cus = static_cast<uint64_t>(p->num_cus);
-  live = 8;
-  for (uint32_t l = 1; l <= 4; l *= 2)
-    if (p->batch <= cus * l) {
-      live = l;
-      break;
-    }
-  const uint64_t blocks = (p->batch + live - 1) / live;
-  const uint64_t iters = blocks >= 4 * cus ? 2 : 1;
-  grid = static_cast<uint32_t>(std::max<uint64_t>(std::min<uint64_t>(blocks, cus), (blocks + iters - 1) / iters));
 }
 
 int create_fused(tfft_conv_plan* p) {
@@ -187,8 +118,8 @@ int create_composed(tfft_conv_plan* p) {
   io.in_batch_stride = 2 * p->n;
   io.out_batch_stride = p->out_stride;
   io.input_order = transposed ? TFFT_ORDER_TRANSPOSED : TFFT_ORDER_NATURAL;
-  int rc = pass_through(tfft_plan_create(p->n, p->batch, p->device, &fo, &p->fwd));
-  if (rc == TFFT_OK) rc = pass_through(tfft_plan_create(p->n, p->batch, p->device, &io, &p->inv));
+  int rc = pass_tfft(tfft_plan_create(p->n, p->batch, p->device, &fo, &p->fwd));
+  if (rc == TFFT_OK) rc = pass_tfft(tfft_plan_create(p->n, p->batch, p->device, &io, &p->inv));
   if (rc) return rc;
   p->spec_bytes = round256(static_cast<size_t>(p->batch) * p->n * 4);
   p->sub_bytes = round256(std::max(tfft_plan_workspace_bytes(p->fwd), tfft_plan_workspace_bytes(p->inv)));
@@ -221,9 +152,7 @@ int tfft_conv_describe(uint64_t n, uint64_t batch, uint64_t filters, int flags, 
     if (rc) return rc;
     out = f + " | cmul | " + i;
   }
-  if (out.size() + 1 > bytes) return fail(TFFT_ERR_ARG, "buffer too small");
-  std::memcpy(buf, out.c_str(), out.size() + 1);
-  return TFFT_OK;
+  return copy_text(out, buf, bytes);
 }
 
 int tfft_conv_plan_create(uint64_t n, uint64_t batch, uint64_t filters, int device_id, uint64_t in_batch_stride,
@@ -234,8 +163,8 @@ int tfft_conv_plan_create(uint64_t n, uint64_t batch, uint64_t filters, int devi
   int rc = check_shape(n, batch, filters, flags);
   if (rc == TFFT_OK) rc = check_stride(n, in_batch_stride, "in");
   if (rc == TFFT_OK) rc = check_stride(n, out_batch_stride, "out");
-  if (rc == TFFT_OK) rc = check_abi();
-  if (rc == TFFT_OK) rc = pass_through(tfft_device_check(device_id));
+  if (rc == TFFT_OK) rc = check_abi("libtfft_conv.so");
+  if (rc == TFFT_OK) rc = pass_tfft(tfft_device_check(device_id));
   if (rc) return rc;
   int prev = 0;
   CONV_HIP(hipGetDevice(&prev));
@@ -257,12 +186,7 @@ int tfft_conv_plan_create(uint64_t n, uint64_t batch, uint64_t filters, int devi
     if (e != hipSuccess) rc = hip_fail(e, "hipMalloc(filter image)");
   }
   (void)hipSetDevice(prev);
-  if (rc) {
-    const std::string keep = g_err;
-    tfft_conv_plan_destroy(p);
-    g_err = keep;
-    return rc;
-  }
+  if (rc) return fail_create(p, rc, tfft_conv_plan_destroy);
   *out = p;
   return TFFT_OK;
 }
@@ -281,9 +205,8 @@ int tfft_conv_plan_set_filter(tfft_conv_plan* p, const void* h_re, const void* h
   g_err.clear();
   if (!p) return fail(TFFT_ERR_ARG, "null plan");
   if (!h_re || !h_im) return fail(TFFT_ERR_ARG, "null filter pointer");
-  int cur = 0;
-  CONV_HIP(hipGetDevice(&cur));
-  if (cur != p->device) return fail(TFFT_ERR_ARG, "plan was created for another device than the current one");
+  const int cur_rc = check_current(p->device);
+  if (cur_rc) return cur_rc;
   const size_t plane = static_cast<size_t>(p->filters) * p->n;
   std::vector<uint16_t> re(plane), im(plane), img(2 * plane);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -329,8 +252,8 @@ int tfft_conv_plan_prepare(tfft_conv_plan* p) {
   CONV_HIP(hipGetDevice(&prev));
   CONV_HIP(hipSetDevice(p->device));
   int rc = ensure_workspace(p);
-  if (rc == TFFT_OK) rc = pass_through(tfft_plan_prepare(p->fwd));
-  if (rc == TFFT_OK) rc = pass_through(tfft_plan_prepare(p->inv));
+  if (rc == TFFT_OK) rc = pass_tfft(tfft_plan_prepare(p->fwd));
+  if (rc == TFFT_OK) rc = pass_tfft(tfft_plan_prepare(p->inv));
   (void)hipSetDevice(prev);
   return rc;
 }
@@ -346,19 +269,18 @@ int tfft_conv_exec(const tfft_conv_plan* p, const void* in_re, const void* in_im
   const bool same_re = in_re == out_re, same_im = in_im == out_im;
   if ((same_re || same_im) && p->in_stride != p->out_stride)
     return fail(TFFT_ERR_ARG, "in-place execution needs equal input and output batch strides");
-  if ((!same_re && planes_overlap(in_re, p->in_stride, out_re, p->out_stride, p->batch, p->n)) ||
-      (!same_im && planes_overlap(in_im, p->in_stride, out_im, p->out_stride, p->batch, p->n)) ||
-      planes_overlap(in_re, p->in_stride, out_im, p->out_stride, p->batch, p->n) ||
-      planes_overlap(in_im, p->in_stride, out_re, p->out_stride, p->batch, p->n) ||
-      planes_overlap(out_re, p->out_stride, out_im, p->out_stride, p->batch, p->n))
+  if ((!same_re && seqs_overlap(in_re, p->in_stride, p->n, out_re, p->out_stride, p->n, p->batch)) ||
+      (!same_im && seqs_overlap(in_im, p->in_stride, p->n, out_im, p->out_stride, p->n, p->batch)) ||
+      seqs_overlap(in_re, p->in_stride, p->n, out_im, p->out_stride, p->n, p->batch) ||
+      seqs_overlap(in_im, p->in_stride, p->n, out_re, p->out_stride, p->n, p->batch) ||
+      seqs_overlap(out_re, p->out_stride, p->n, out_im, p->out_stride, p->n, p->batch))
     return fail(TFFT_ERR_ARG, "input and output planes overlap without being identical (only exact in-place or disjoint planes are supported)");
-  int cur = 0;
-  CONV_HIP(hipGetDevice(&cur));
-  if (cur != p->device) return fail(TFFT_ERR_ARG, "plan was created for another device than the current one");
+  const int cur_rc = check_current(p->device);
+  if (cur_rc) return cur_rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (p->fused) {
     uint32_t live, grid;
-    conv4096_shape(p, live, grid);
+    conv_shape(p->batch, p->num_cus, 0, live, grid);      // no launch_iters in this ABI: the default shape
     hipLaunchKernelGGL(conv4096::conv4096_kernel, dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s, static_cast<const uint16_t*>(in_re),
                        static_cast<const uint16_t*>(in_im), static_cast<uint16_t*>(out_re), static_cast<uint16_t*>(out_im), p->in_stride,
                        p->out_stride, static_cast<uint32_t>(p->batch), live, static_cast<uint32_t>(p->filters),
@@ -369,14 +291,14 @@ int tfft_conv_exec(const tfft_conv_plan* p, const void* in_re, const void* in_im
   int rc = ensure_workspace(p);
   if (rc) return rc;
   uint16_t* const spec = static_cast<uint16_t*>(p->ws);
-  rc = pass_through(tfft_exec(p->fwd, in_re, in_im, spec, spec + p->n, s));
+  rc = pass_tfft(tfft_exec(p->fwd, in_re, in_im, spec, spec + p->n, s));
   if (rc) return rc;
   const uint64_t total = p->batch * (p->n / 8);
   const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((total + cmul::kThreads - 1) / cmul::kThreads, static_cast<uint64_t>(p->num_cus) * 32));
   hipLaunchKernelGGL(cmul::cmul_kernel, dim3(grid), dim3(cmul::kThreads), 0, s, spec, p->d_filter, static_cast<uint32_t>(ilog2(p->n / 8)), total,
                      static_cast<uint32_t>(p->filters), static_cast<float>(p->n));
   CONV_HIP(hipGetLastError());
-  return pass_through(tfft_exec_inverse(p->inv, spec, spec + p->n, out_re, out_im, s));
+  return pass_tfft(tfft_exec_inverse(p->inv, spec, spec + p->n, out_re, out_im, s));
 }
 
 int tfft_conv_plan_num_launches(const tfft_conv_plan* p) {
@@ -394,17 +316,15 @@ int tfft_conv_plan_kernels(const tfft_conv_plan* p, char* buf, size_t bytes) {
   } else {
     std::vector<char> tmp(1 << 16);
     const int a = tfft_plan_kernels(p->fwd, tmp.data(), tmp.size());
-    if (a < 0) return pass_through(a);
+    if (a < 0) return pass_tfft(a);
     out = tmp.data();
     out += "cmul::cmul_kernel\n";
     const int b = tfft_plan_kernels(p->inv, tmp.data(), tmp.size());
-    if (b < 0) return pass_through(b);
+    if (b < 0) return pass_tfft(b);
     out += tmp.data();
     lines = a + 1 + b;
   }
-  if (!buf || out.size() + 1 > bytes) return fail(TFFT_ERR_ARG, "buffer too small (" + std::to_string(out.size() + 1) + " bytes needed)");
-  std::memcpy(buf, out.c_str(), out.size() + 1);
-  return lines;
+  return kernel_names(out, lines, buf, bytes);
 }
 
 }  // extern "C"

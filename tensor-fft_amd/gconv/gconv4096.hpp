@@ -32,15 +32,6 @@ using k4096::s4;
 using k4096::u2;
 using k4096::u4;
 
-// slot of bin k in a plane of the filter image: conv4096::filter_slot / lconv4096::filter_slot restated.
-// tests/test_gpu_gconv.py holds it to the shipped kernel: conv4096_kernel, given the plan's natural-order spectrum, must reproduce
-// this kernel's output bit for bit.
-__host__ __device__ constexpr uint32_t filter_slot(uint32_t k) {
-  const uint32_t k0 = k & 15, k1 = (k >> 4) & 15, k2 = k >> 8;
-  const uint32_t half = k0 >> 3, j = k0 & 7, g = k2 >> 2, r2 = k2 & 3;
-  return ((half * 4 + r2) * 64 + 16 * g + k1) * 8 + j;
-}
-
 // eight binary16 products, each rounded once (v_pk_mul_f16 x 4)
 __device__ __forceinline__ u4 mul8(u4 a, u4 b) { return __builtin_bit_cast(u4, __builtin_bit_cast(h8, a) * __builtin_bit_cast(h8, b)); }
 

@@ -25,15 +25,6 @@ using k4096::s4;
 using k4096::u2;
 using k4096::u4;
 
-// slot of bin k in a plane of the filter image: conv4096::filter_slot (conv/conv4096.hpp) restated, because including that header
-// would emit conv4096_kernel into this code object as well. tests/test_gpu_lconv.py holds the two to each other: the shipped
-// kernel, given the natural-order spectrum, must reproduce this kernel's output bit for bit.
-__host__ __device__ constexpr uint32_t filter_slot(uint32_t k) {
-  const uint32_t k0 = k & 15, k1 = (k >> 4) & 15, k2 = k >> 8;
-  const uint32_t half = k0 >> 3, j = k0 & 7, g = k2 >> 2, r2 = k2 & 3;
-  return ((half * 4 + r2) * 64 + 16 * g + k1) * 8 + j;
-}
-
 // one plane's share of 1-KiB block mm by LDS-DMA, nt (the statement of k4096::dma_in for a single plane; called under the
 // lanes' own predicate: M0 is written by the scalar unit whatever the mask, the load obeys it, and lane l's 16 bytes land at
 // dst + 16 l whichever other lanes are off)

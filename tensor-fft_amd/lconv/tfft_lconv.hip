@@ -2,85 +2,24 @@
 //
 // Layered on libtfft_conv.so and libtfft.so through their public headers only (the sub-plan of the composed path,
 // tfft_device_check, tfft_abi_version); from csrc/ it takes k4096.hpp, header only, for the device helpers and
-// the constant tables of the fused kernel (the add-on uploads a copy of its own).
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <complex>
-#include <cstring>
-#include <mutex>
-#include <string>
-#include <vector>
-
+// the constant tables of the fused kernel (the add-on uploads a copy of its own). The fp64 spectrum builder, the overlap test, the
+// error plumbing and the launch shape come from conv/host_math.hpp and conv/host_plumbing.hpp, the two headers every
+// convolution library includes.
 #include "../../include/tfft_lconv.h"
 #include "lconv4096.hpp"
 #include "pack.hpp"
+#include "../conv/host_plumbing.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-int hip_fail(hipError_t e, const char* what) { return fail(TFFT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-// a failing call into libtfft_conv.so / libtfft.so: its message becomes ours
-int pass_conv(int rc) {
-  if (rc != TFFT_OK) g_err = tfft_conv_last_error();
-  return rc;
-}
-int pass_tfft(int rc) {
-  if (rc != TFFT_OK) g_err = tfft_last_error();
-  return rc;
-}
-#define LCONV_HIP(call)                               \
-  do {                                                \
-    const hipError_t e_ = (call);                     \
-    if (e_ != hipSuccess) return hip_fail(e_, #call); \
-  } while (0)
-
-inline bool is_pow2(uint64_t v) { return v && !(v & (v - 1)); }
-inline int ilog2(uint64_t v) {
-  int l = 0;
-  while (v >>= 1) ++l;
-  return l;
-}
-inline size_t round256(size_t v) { return (v + 255) & ~size_t{255}; }
-
-constexpr uint64_t kMinN = 256, kMaxN = uint64_t{1} << 26;
-
-int check_abi() {
-  static const int version = tfft_abi_version();
-  if (version != TFFT_ABI_VERSION)
-    return fail(TFFT_ERR_ARG, "libtfft.so speaks ABI " + std::to_string(version) + ", libtfft_lconv.so was built against ABI " +
-                                  std::to_string(TFFT_ABI_VERSION) + ": rebuild the add-on");
-  return TFFT_OK;
-}
-
-uint64_t fft_length(uint64_t length, uint64_t taps) {
-  if (!length || !taps || length > kMaxN || taps > kMaxN) return 0;
-  const uint64_t need = std::max(length + taps - 1, kMinN);
-  uint64_t n = kMinN;
-  while (n < need) n *= 2;
-  return n > kMaxN ? 0 : n;
-}
 
 int check_shape(uint64_t rows, uint64_t channels, uint64_t length, uint64_t taps, int flags) {
   if (length < 8 || length % 8) return fail(TFFT_ERR_ARG, "length must be a multiple of 8 and at least 8");
   if (taps == 0) return fail(TFFT_ERR_ARG, "taps must be at least 1");
   if (flags & ~TFFT_LCONV_COMPOSED) return fail(TFFT_ERR_ARG, "unknown flag bits (" + std::to_string(flags) + ")");
-  if (rows == 0 || rows > 0xffffffffull) return fail(TFFT_ERR_ARG, "rows must be in [1, 2^32)");
-  if (channels == 0 || channels > 0xffffffffull) return fail(TFFT_ERR_ARG, "channels must be in [1, 2^32)");
-  if (rows * channels > 0xffffffffull) return fail(TFFT_ERR_ARG, "rows * channels must be below 2^32");
+  const int rc = check_rows_channels(rows, channels);
+  if (rc) return rc;
   if (!fft_length(length, taps))
     return fail(TFFT_ERR_ARG, "the transform length (the power of two >= length + taps - 1) must not exceed 2^26");
-  return TFFT_OK;
-}
-int check_stride(uint64_t length, uint64_t stride, const char* which) {
-  if (stride && (stride % 8 || stride < length))
-    return fail(TFFT_ERR_ARG, std::string(which) + "_seq_stride must be 0 or a multiple of 8 that is >= length");
   return TFFT_OK;
 }
 
@@ -91,90 +30,6 @@ inline bool fused_shape(uint64_t length, uint64_t taps, int flags) {
 }
 inline uint64_t plan_length(uint64_t length, uint64_t taps, int flags) { return fused_shape(length, taps, flags) ? 4096 : fft_length(length, taps); }
 
-// Element-exact test whether two sets of sequences (count blocks of len halves, `stride` halves apart) share a half: the test of
-// tfft_conv_exec.
-bool seqs_overlap(const void* pa, uint64_t sa, const void* pb, uint64_t sb, uint64_t count, uint64_t len) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(pa), b = reinterpret_cast<uintptr_t>(pb);
-  const uintptr_t a_end = a + 2 * ((count - 1) * sa + len), b_end = b + 2 * ((count - 1) * sb + len);
-  if (a_end <= b || b_end <= a) return false;
-  if (count == 1 || sa != sb) return true;            // different strides: conservative
-  const uint64_t d = static_cast<uint64_t>(a > b ? a - b : b - a) / 2 % sa;
-  return d < len || sa - d < len;
-}
-
-// ---- binary16 on the host, bit by bit (round to nearest even, one rounding from fp64)
-double from_half(uint16_t h) {
-  const int e = (h >> 10) & 31, m = h & 1023;
-  double v;
-  if (e == 0)
-    v = std::ldexp(static_cast<double>(m), -24);
-  else if (e == 31)
-    v = m ? NAN : INFINITY;
-  else
-    v = std::ldexp(static_cast<double>(m + 1024), e - 25);
-  return (h & 0x8000) ? -v : v;
-}
-uint16_t to_half(double v) {
-  const uint16_t sign = std::signbit(v) ? 0x8000 : 0;
-  if (v != v) return sign | 0x7e00;
-  const double a = std::fabs(v);
-  if (a >= 65520.0) return sign | 0x7c00;
-  if (a == 0.0) return sign;
-  int e2;
-  (void)std::frexp(a, &e2);                                 // a = f * 2^e2, f in [0.5, 1)
-  const int e = std::max(e2 - 1, -14);                      // the binade whose spacing applies (subnormals share the lowest)
-  const long r = std::lrint(std::ldexp(a, 10 - e));         // exact scaling, then the one rounding (to nearest even)
-  if (e == -14 && r < 1024) return sign | static_cast<uint16_t>(r);
-  return sign | static_cast<uint16_t>(((e + 15) << 10) + (r - 1024));    // r = 2048 carries into the exponent
-}
-
-// in-place radix-2 fp64 FFT (forward, unscaled). Twiddles w^k = A[k >> s] B[k & mask] from two tables of about sqrt(n) entries,
-// each entry from sin / cos directly: one product per twiddle, no error growth along a recurrence.
-void fft64(std::vector<std::complex<double>>& a) {
-  const uint64_t n = a.size();
-  const int lg = ilog2(n);
-  for (uint64_t i = 1, j = 0; i < n; ++i) {
-    uint64_t bit = n >> 1;
-    for (; j & bit; bit >>= 1) j ^= bit;
-    j ^= bit;
-    if (i < j) std::swap(a[i], a[j]);
-  }
-  const int s = lg / 2;
-  const uint64_t lo_n = uint64_t{1} << s, hi_n = std::max<uint64_t>(n >> s, 1);
-  std::vector<std::complex<double>> ta(hi_n), tb(lo_n);
-  const double step = -2.0 * M_PI / static_cast<double>(n);
-  for (uint64_t i = 0; i < hi_n; ++i) ta[i] = {std::cos(step * static_cast<double>(i << s)), std::sin(step * static_cast<double>(i << s))};
-  for (uint64_t i = 0; i < lo_n; ++i) tb[i] = {std::cos(step * static_cast<double>(i)), std::sin(step * static_cast<double>(i))};
-  for (uint64_t m = 2; m <= n; m *= 2) {
-    const uint64_t half = m / 2, mul = n / m;
-    for (uint64_t k = 0; k < n; k += m)
-      for (uint64_t j = 0; j < half; ++j) {
-        const uint64_t idx = j * mul;
-        const std::complex<double> w = ta[idx >> s] * tb[idx & (lo_n - 1)];
-        const std::complex<double> u = a[k + j], t = w * a[k + j + half];
-        a[k + j] = u + t;
-        a[k + j + half] = u - t;
-      }
-  }
-}
-
-// one filter: H = FFT of the zero-padded taps, each component rounded once; exactly Hermitian, Im of bins 0 and n / 2 exactly 0
-void spectrum(const uint16_t* taps, uint64_t num_taps, uint64_t n, uint16_t* out_re, uint16_t* out_im) {
-  std::vector<std::complex<double>> a(n);
-  for (uint64_t j = 0; j < num_taps; ++j) a[j] = from_half(taps[j]);
-  fft64(a);
-  for (uint64_t k = 0; k <= n / 2; ++k) {
-    const uint16_t re = to_half(a[k].real());
-    const uint16_t im = (k == 0 || k == n / 2) ? 0 : to_half(a[k].imag());
-    out_re[k] = re;
-    out_im[k] = im;
-    if (k && k < n / 2) {
-      out_re[n - k] = re;
-      out_im[n - k] = (im & 0x7fff) ? (im ^ 0x8000) : 0;        // conj; a zero stays +0
-    }
-  }
-}
-
 }  // namespace
 
 struct tfft_lconv_plan {
@@ -183,7 +38,7 @@ struct tfft_lconv_plan {
   int device = 0, flags = 0, num_cus = 256;
   bool fused = false;
   void* d_tables = nullptr;          // fused: F / twiddle / G / H of k4096::build_tables
-  uint16_t* d_filter = nullptr;      // fused: [channels][RE 4096 | IM 4096] in conv4096::filter_slot order
+  uint16_t* d_filter = nullptr;      // fused: [channels][RE 4096 | IM 4096] in filter_slot order
   uint16_t* d_spec = nullptr;        // [RE: channels x n | IM: channels x n], natural bin order (tfft_lconv_plan_spectrum)
   bool have_taps = false;
   tfft_conv_plan* sub = nullptr;     // composed: in place on the blocks
@@ -206,42 +61,21 @@ int ensure_workspace(const tfft_lconv_plan* p) {
   const size_t need = p->block_bytes + p->sub_bytes;
   if (!need || p->ws) return TFFT_OK;
   void* mem = nullptr;
-  LCONV_HIP(hipMalloc(&mem, need));
+  CONV_HIP(hipMalloc(&mem, need));
   p->ws = mem;
   p->ws_bytes = need;
   p->ws_owned = true;
   return bind_workspace(p);
 }
 
-// launch shape of the fused kernel: conv4096_kernel's (tfft_conv.hip, conv4096_shape) applied to the item count; launch_iters as
-// tfft_lconv_opts states it
-void lconv4096_shape(const tfft_lconv_plan* p, uint32_t& live, uint32_t& grid) {
-  const uint64_t cus = static_cast<uint64_t>(p->num_cus);
-  live = 8;
-  for (uint32_t l = 1; l <= 4; l *= 2)
-    if (p->items <= cus * l) {
-      live = l;
-      break;
-    }
-  const uint64_t blocks = (p->items + live - 1) / live;
-  if (p->launch_iters >= TFFT_LAUNCH_PERSISTENT) {
-    grid = static_cast<uint32_t>(std::min(blocks, cus));
-  } else if (p->launch_iters) {
-    grid = static_cast<uint32_t>((blocks + p->launch_iters - 1) / p->launch_iters);
-  } else {
-    const uint64_t iters = blocks >= 4 * cus ? 2 : 1;
-    grid = static_cast<uint32_t>(std::max<uint64_t>(std::min<uint64_t>(blocks, cus), (blocks + iters - 1) / iters));
-  }
-}
-
 int create_fused(tfft_lconv_plan* p) {
   std::vector<uint8_t> blob;
   k4096::build_tables(blob);
-  LCONV_HIP(hipMalloc(&p->d_tables, k4096::kOffF1n));
-  LCONV_HIP(hipMemcpy(p->d_tables, blob.data(), k4096::kOffF1n, hipMemcpyHostToDevice));
-  LCONV_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_filter), static_cast<size_t>(p->channels) * 8192 * 2));
+  CONV_HIP(hipMalloc(&p->d_tables, k4096::kOffF1n));
+  CONV_HIP(hipMemcpy(p->d_tables, blob.data(), k4096::kOffF1n, hipMemcpyHostToDevice));
+  CONV_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_filter), static_cast<size_t>(p->channels) * 8192 * 2));
   // more than 64 KiB of dynamic LDS: opt in now, so that an execution is a pure launch
-  LCONV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lconv4096::lconv4096_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, k4096::kLdsBytes));
+  CONV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lconv4096::lconv4096_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, k4096::kLdsBytes));
   return TFFT_OK;
 }
 
@@ -270,7 +104,7 @@ int tfft_lconv_spectrum_host(const uint16_t* taps, uint64_t num_taps, uint64_t n
   if (!taps || !out_re || !out_im) return fail(TFFT_ERR_ARG, "null pointer");
   if (!is_pow2(n) || n < 2 || n > kMaxN) return fail(TFFT_ERR_ARG, "n must be a power of two in 2 .. 2^26");
   if (num_taps == 0 || num_taps > n) return fail(TFFT_ERR_ARG, "the number of taps must be in [1, n]");
-  spectrum(taps, num_taps, n, out_re, out_im);
+  spectrum(taps, num_taps, 0, n, out_re, out_im);
   return TFFT_OK;
 }
 
@@ -289,9 +123,7 @@ int tfft_lconv_describe(uint64_t length, uint64_t taps, uint64_t rows, uint64_t 
     if (rc) return rc;
     out = std::string("pack | ") + sub + " | crop";
   }
-  if (out.size() + 1 > bytes) return fail(TFFT_ERR_ARG, "buffer too small");
-  std::memcpy(buf, out.c_str(), out.size() + 1);
-  return TFFT_OK;
+  return copy_text(out, buf, bytes);
 }
 
 int tfft_lconv_plan_create(uint64_t rows, uint64_t channels, uint64_t length, uint64_t taps, int device_id, const tfft_lconv_opts* opts,
@@ -300,23 +132,18 @@ int tfft_lconv_plan_create(uint64_t rows, uint64_t channels, uint64_t length, ui
   if (!out) return fail(TFFT_ERR_ARG, "null plan pointer");
   *out = nullptr;
   tfft_lconv_opts o = TFFT_LCONV_OPTS_INIT;
-  if (opts) {
-    if (opts->struct_size != sizeof(tfft_lconv_opts))
-      return fail(TFFT_ERR_ARG, "tfft_lconv_opts.struct_size = " + std::to_string(opts->struct_size) + " is not the size of a layout this library knows (" +
-                                    std::to_string(sizeof(tfft_lconv_opts)) + ")");
-    if (opts->reserved_) return fail(TFFT_ERR_ARG, "tfft_lconv_opts.reserved_ must be 0");
-    o = *opts;
-  }
-  int rc = check_shape(rows, channels, length, taps, o.flags);
-  if (rc == TFFT_OK) rc = check_stride(length, o.in_seq_stride, "in");
-  if (rc == TFFT_OK) rc = check_stride(length, o.out_seq_stride, "out");
-  if (rc == TFFT_OK && o.launch_iters > TFFT_LAUNCH_PERSISTENT) rc = fail(TFFT_ERR_ARG, "launch_iters must be 0 .. 65535");
-  if (rc == TFFT_OK) rc = check_abi();
+  int rc = take_opts(opts, "tfft_lconv_opts", o);
+  if (rc) return rc;
+  rc = check_shape(rows, channels, length, taps, o.flags);
+  if (rc == TFFT_OK) rc = check_seq_stride(length, o.in_seq_stride, "in");
+  if (rc == TFFT_OK) rc = check_seq_stride(length, o.out_seq_stride, "out");
+  if (rc == TFFT_OK) rc = check_launch_iters(o.launch_iters);
+  if (rc == TFFT_OK) rc = check_abi("libtfft_lconv.so");
   if (rc == TFFT_OK) rc = pass_tfft(tfft_device_check(device_id));
   if (rc) return rc;
   int prev = 0;
-  LCONV_HIP(hipGetDevice(&prev));
-  LCONV_HIP(hipSetDevice(device_id));
+  CONV_HIP(hipGetDevice(&prev));
+  CONV_HIP(hipSetDevice(device_id));
   tfft_lconv_plan* p = new tfft_lconv_plan;
   p->rows = rows;
   p->channels = channels;
@@ -338,12 +165,7 @@ int tfft_lconv_plan_create(uint64_t rows, uint64_t channels, uint64_t length, ui
     if (e != hipSuccess) rc = hip_fail(e, "hipMalloc(filter spectrum)");
   }
   (void)hipSetDevice(prev);
-  if (rc) {
-    const std::string keep = g_err;
-    tfft_lconv_plan_destroy(p);
-    g_err = keep;
-    return rc;
-  }
+  if (rc) return fail_create(p, rc, tfft_lconv_plan_destroy);
   *out = p;
   return TFFT_OK;
 }
@@ -351,9 +173,7 @@ int tfft_lconv_plan_create(uint64_t rows, uint64_t channels, uint64_t length, ui
 void tfft_lconv_plan_destroy(tfft_lconv_plan* p) {
   if (!p) return;
   tfft_conv_plan_destroy(p->sub);
-  if (p->d_tables) (void)hipFree(p->d_tables);
-  if (p->d_filter) (void)hipFree(p->d_filter);
-  if (p->d_spec) (void)hipFree(p->d_spec);
+  destroy_base(p);
   if (p->ws && p->ws_owned) (void)hipFree(p->ws);
   delete p;
 }
@@ -362,29 +182,23 @@ int tfft_lconv_plan_set_taps(tfft_lconv_plan* p, const void* taps, void* stream)
   g_err.clear();
   if (!p) return fail(TFFT_ERR_ARG, "null plan");
   if (!taps) return fail(TFFT_ERR_ARG, "null taps pointer");
-  int cur = 0;
-  LCONV_HIP(hipGetDevice(&cur));
-  if (cur != p->device) return fail(TFFT_ERR_ARG, "plan was created for another device than the current one");
+  const int cur_rc = check_current(p->device);
+  if (cur_rc) return cur_rc;
   const size_t plane = static_cast<size_t>(p->channels) * p->n;
   std::vector<uint16_t> h(static_cast<size_t>(p->channels) * p->taps), spec(2 * plane);
   hipStream_t s = static_cast<hipStream_t>(stream);
   // through the host: the spectrum is built once per filter, not per execution. Everything enqueued on `stream` before the call
   // (the kernel that produced the taps) is waited for; executions still in flight keep reading the old spectrum until then, so the
   // device is drained before it is replaced.
-  LCONV_HIP(hipMemcpyAsync(h.data(), taps, h.size() * 2, hipMemcpyDeviceToHost, s));
-  LCONV_HIP(hipStreamSynchronize(s));
-  for (uint64_t c = 0; c < p->channels; ++c) spectrum(h.data() + c * p->taps, p->taps, p->n, spec.data() + c * p->n, spec.data() + plane + c * p->n);
-  if (p->have_taps) LCONV_HIP(hipDeviceSynchronize());
-  LCONV_HIP(hipMemcpy(p->d_spec, spec.data(), spec.size() * 2, hipMemcpyHostToDevice));
+  CONV_HIP(hipMemcpyAsync(h.data(), taps, h.size() * 2, hipMemcpyDeviceToHost, s));
+  CONV_HIP(hipStreamSynchronize(s));
+  for (uint64_t c = 0; c < p->channels; ++c) spectrum(h.data() + c * p->taps, p->taps, 0, p->n, spec.data() + c * p->n, spec.data() + plane + c * p->n);
+  if (p->have_taps) CONV_HIP(hipDeviceSynchronize());
+  CONV_HIP(hipMemcpy(p->d_spec, spec.data(), spec.size() * 2, hipMemcpyHostToDevice));
   if (p->fused) {
     std::vector<uint16_t> img(2 * plane);
-    for (uint64_t c = 0; c < p->channels; ++c)
-      for (uint32_t k = 0; k < 4096; ++k) {
-        const uint32_t slot = lconv4096::filter_slot(k);
-        img[c * 8192 + slot] = spec[c * 4096 + k];
-        img[c * 8192 + 4096 + slot] = spec[plane + c * 4096 + k];
-      }
-    LCONV_HIP(hipMemcpy(p->d_filter, img.data(), img.size() * 2, hipMemcpyHostToDevice));
+    for (uint64_t c = 0; c < p->channels; ++c) filter_image(spec.data() + c * 4096, spec.data() + plane + c * 4096, false, img.data() + c * 8192);
+    CONV_HIP(hipMemcpy(p->d_filter, img.data(), img.size() * 2, hipMemcpyHostToDevice));
   } else {
     const int rc = pass_conv(tfft_conv_plan_set_filter(p->sub, p->d_spec, p->d_spec + plane, stream));
     if (rc) return rc;
@@ -399,9 +213,9 @@ int tfft_lconv_plan_spectrum(const tfft_lconv_plan* p, void* h_re, void* h_im) {
   if (!h_re || !h_im) return fail(TFFT_ERR_ARG, "null spectrum pointer");
   if (!p->have_taps) return fail(TFFT_ERR_ARG, "no taps: call tfft_lconv_plan_set_taps first");
   const size_t plane = static_cast<size_t>(p->channels) * p->n;
-  LCONV_HIP(hipMemcpy(h_re, p->d_spec, plane * 2, hipMemcpyDeviceToDevice));
-  LCONV_HIP(hipMemcpy(h_im, p->d_spec + plane, plane * 2, hipMemcpyDeviceToDevice));
-  LCONV_HIP(hipDeviceSynchronize());
+  CONV_HIP(hipMemcpy(h_re, p->d_spec, plane * 2, hipMemcpyDeviceToDevice));
+  CONV_HIP(hipMemcpy(h_im, p->d_spec + plane, plane * 2, hipMemcpyDeviceToDevice));
+  CONV_HIP(hipDeviceSynchronize());
   return TFFT_OK;
 }
 
@@ -428,8 +242,8 @@ int tfft_lconv_plan_prepare(tfft_lconv_plan* p) {
   if (!p) return fail(TFFT_ERR_ARG, "null plan");
   if (p->fused) return TFFT_OK;
   int prev = 0;
-  LCONV_HIP(hipGetDevice(&prev));
-  LCONV_HIP(hipSetDevice(p->device));
+  CONV_HIP(hipGetDevice(&prev));
+  CONV_HIP(hipSetDevice(p->device));
   int rc = ensure_workspace(p);
   if (rc == TFFT_OK) rc = pass_conv(tfft_conv_plan_prepare(p->sub));
   (void)hipSetDevice(prev);
@@ -445,21 +259,20 @@ int tfft_lconv_exec(const tfft_lconv_plan* p, const void* in, void* out, void* s
   const uint64_t seqs = p->rows * p->channels;
   if (in == out) {
     if (p->in_stride != p->out_stride) return fail(TFFT_ERR_ARG, "in-place execution needs equal input and output sequence strides");
-  } else if (seqs_overlap(in, p->in_stride, out, p->out_stride, seqs, p->length)) {
+  } else if (seqs_overlap(in, p->in_stride, p->length, out, p->out_stride, p->length, seqs)) {
     return fail(TFFT_ERR_ARG, "input and output overlap without being identical (only exact in-place or disjoint sequences are supported)");
   }
-  int cur = 0;
-  LCONV_HIP(hipGetDevice(&cur));
-  if (cur != p->device) return fail(TFFT_ERR_ARG, "plan was created for another device than the current one");
+  const int cur_rc = check_current(p->device);
+  if (cur_rc) return cur_rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint32_t chunks = static_cast<uint32_t>(p->length / 8);
   if (p->fused) {
     uint32_t live, grid;
-    lconv4096_shape(p, live, grid);
+    conv_shape(p->items, p->num_cus, p->launch_iters, live, grid);
     hipLaunchKernelGGL(lconv4096::lconv4096_kernel, dim3(grid), dim3(k4096::kThreads), k4096::kLdsBytes, s, static_cast<const uint16_t*>(in),
                        static_cast<uint16_t*>(out), p->in_stride, p->out_stride, static_cast<uint32_t>(p->rows), static_cast<uint32_t>(p->channels),
                        chunks, static_cast<uint32_t>(p->items), live, static_cast<const uint8_t*>(p->d_tables), p->d_filter);
-    LCONV_HIP(hipGetLastError());
+    CONV_HIP(hipGetLastError());
     return TFFT_OK;
   }
   int rc = ensure_workspace(p);
@@ -469,12 +282,12 @@ int tfft_lconv_exec(const tfft_lconv_plan* p, const void* in, void* out, void* s
   const uint64_t total_in = p->items * 2 * (p->n / 8), total_out = seqs * chunks;
   hipLaunchKernelGGL(lconv_copy::pack_kernel, dim3(copy_grid(p, total_in)), dim3(lconv_copy::kThreads), 0, s, static_cast<const uint16_t*>(in), blocks,
                      p->in_stride, static_cast<uint32_t>(p->rows), static_cast<uint32_t>(p->channels), chunks, log_n8, total_in);
-  LCONV_HIP(hipGetLastError());
+  CONV_HIP(hipGetLastError());
   rc = pass_conv(tfft_conv_exec(p->sub, blocks, blocks + p->n, blocks, blocks + p->n, s));
   if (rc) return rc;
   hipLaunchKernelGGL(lconv_copy::crop_kernel, dim3(copy_grid(p, total_out)), dim3(lconv_copy::kThreads), 0, s, blocks, static_cast<uint16_t*>(out), p->out_stride,
                      static_cast<uint32_t>(p->channels), chunks, log_n8, total_out);
-  LCONV_HIP(hipGetLastError());
+  CONV_HIP(hipGetLastError());
   return TFFT_OK;
 }
 
@@ -497,9 +310,7 @@ int tfft_lconv_plan_kernels(const tfft_lconv_plan* p, char* buf, size_t bytes) {
     out = std::string("lconv_copy::pack_kernel\n") + tmp.data() + "lconv_copy::crop_kernel\n";
     lines = a + 2;
   }
-  if (!buf || out.size() + 1 > bytes) return fail(TFFT_ERR_ARG, "buffer too small (" + std::to_string(out.size() + 1) + " bytes needed)");
-  std::memcpy(buf, out.c_str(), out.size() + 1);
-  return lines;
+  return kernel_names(out, lines, buf, bytes);
 }
 
 }  // extern "C"

@@ -295,6 +295,18 @@ def test_rotor_covers_every_item_once(tmp_path):
     assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip() == "ok"
 
 
+def test_conv_host_math(tmp_path):
+    """tensor-fft_amd/conv/host_math.hpp, the host arithmetic the nine convolution libraries share, on its own: seqs_overlap
+    against brute force (never a missed shared half; exact at equal strides), to_half(from_half(h)) == h for all 65536 patterns,
+    halo / hop / segments against the closed forms of tests/sconv_ref.py, filter_slot a permutation of 0 .. 4095."""
+    import subprocess
+
+    exe = str(tmp_path / "conv_host_math")
+    _hipcc_host(os.path.join(ROOT, "tests", "cxx", "conv_host_math.cpp"), exe)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout
+
+
 def test_reference_style_mains_compile_against_the_shim(tmp_path):
     """A main() that makes the reference's calls in the reference's order (ExampleBatchFFT.cu:20-85, ExampleSingleFFT.cu)
     builds against include/tensor_fft.hpp with hipcc. (Running it needs a GPU: tests/test_gpu_parity.py.)"""
