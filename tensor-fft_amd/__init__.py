@@ -3,7 +3,7 @@
 Import name: ``tensor_fft_amd`` (see ``tensor_fft_amd.py`` at the repository
 root; the directory carries the upstream project's hyphen).
 
-Nine layers, all thin:
+Eleven layers, all thin:
 
 * :mod:`.capi` — ctypes binding of the C ABI ``include/tfft.h`` in
   ``libtfft.so`` (hand-written HIP, built in-tree by ``__graft_entry__.build``).
@@ -29,6 +29,9 @@ Nine layers, all thin:
 * :mod:`.cconv` — ctypes binding of the carried convolution add-on ``include/tfft_cconv.h`` in ``libtfft_cconv.so`` (the plans of
   :mod:`.sconv` and :mod:`.bconv` on a chunk of a longer sequence, with the history in front of x and the future behind g read in
   place, and the ``torch.autograd`` hook over them; layered on ``libtfft_conv.so`` and ``libtfft.so``; no fallback).
+* :mod:`.stft` — ctypes binding of the short-time Fourier transform add-on ``include/tfft_stft.h`` in ``libtfft_stft.so`` (hopped,
+  windowed frames of 4096 samples of long real signals to half spectra in one kernel; layered on ``libtfft_conv.so`` and
+  ``libtfft.so``; no fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -60,6 +63,8 @@ from .cconv import (TfftChunkedConvGradPlan, TfftChunkedConvPlan, cconv_cache_cl
 from .gcconv import (TfftGatedChunkedConvGradPlan, TfftGatedChunkedConvPlan, differentiable_gated_chunked_causal_conv,  # noqa: F401
                      gated_chunked_causal_conv, gated_chunked_causal_conv_input_grad, gated_chunked_causal_conv_tap_grad,
                      gcconv_cache_clear, gcconv_describe, gcconv_geometry, gcconv_lib_path, load_gcconv_library)
+from .stft import (StftOpts, TfftStftPlan, load_stft_library, stft, stft_cache_clear, stft_describe, stft_geometry,  # noqa: F401
+                   stft_lib_path)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -93,6 +98,7 @@ __all__ = [
     "TfftGatedChunkedConvGradPlan", "TfftGatedChunkedConvPlan", "differentiable_gated_chunked_causal_conv", "gated_chunked_causal_conv",
     "gated_chunked_causal_conv_input_grad", "gated_chunked_causal_conv_tap_grad", "gcconv_cache_clear", "gcconv_describe", "gcconv_geometry",
     "gcconv_lib_path", "load_gcconv_library",
+    "StftOpts", "TfftStftPlan", "load_stft_library", "stft", "stft_cache_clear", "stft_describe", "stft_geometry", "stft_lib_path",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]
