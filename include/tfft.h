@@ -215,7 +215,15 @@ int tfft_plan_opts_known_size(size_t bytes);
  *   ONCE        one scaling step: every stage unscaled and a single exact factor 1/N applied in fp32 at the last fp32
  *               multiply of the plan (the inter-stage twiddle of its last kernel). Result = DFT(x)/N. Small inputs
  *               keep their precision longest (nothing is pushed towards fp16 subnormals before the last stage); the
- *               stages in front of the scaling step can overflow when 16^s * max|x| > 65504 (s = stages before it). */
+ *               stages in front of the scaling step can overflow when 16^s * max|x| > 65504 (s = stages before it).
+ *               In the single kernels of N = 256 .. 32768 that multiply lies in FRONT of the last MFMA stage, whose operand
+ *               is binary16: with the whole 1/N on it the operand is 1/16 of SEQUENTIAL's, closer to the subnormals, not
+ *               farther. N = 512 .. 4096 therefore keep the last stage's 1/16 in its constant operand and multiply by 16/N:
+ *               from that multiply on they are SEQUENTIAL bit for bit. N = 256 and N = 8192 .. 32768 carry the whole 1/N
+ *               on the multiply.
+ *           "Away from underflow" is a condition on the intermediates, not only on the result: at N = 4096 an impulse
+ *           of 1024 has 2636 subnormal components behind the second stage under SEQUENTIAL and ONCE and none under NONE
+ *           (products of rounded constants where the exact component is 0; tests/test_stage_model_host.py). */
 enum { TFFT_SCALE_SEQUENTIAL = 0, TFFT_SCALE_NONE = 1, TFFT_SCALE_ONCE = 2 };
 
 /* tfft_plan_opts.output_order / input_order.

@@ -7,7 +7,8 @@ every element instead. For each transform t:
 
 u is the binary16 ulp of the largest output bin, the unit of profiles/r2_ulp_distances.txt. A rel-L2 bound is kept as well, per
 transform and, from 8192 bins on, per 16-column tile of the [256][bins / 256] view (a column pass's unit of work in natural-order
-1D output): a relative error of 2^-9 on one tile, a wrong twiddle, is 2 to 4 ulps of the largest bin at most and can hide under K.
+1D output): a relative error of 2^-9 on one tile, a wrong twiddle, is 2 to 4 ulps of the largest bin at most and can hide under K
+(for the single-pass kernels N = 256 .. 4096 tests/test_gpu_basis_sweep.py closes that: every basis vector against the stage arithmetic).
 A tile is judged against its own energy or the average tile's, whichever is larger, so a near-empty tile of a sparse spectrum
 raises no false alarm. K is set per arithmetic class from profiles/per_kernel_ulps.txt (tools/accuracy_per_kernel.py: the worst error of every
 kernel instantiation over tests/test_gpu_kernel_matrix.py's cases and three seeds; K = the smallest half-integer >= 1.5 x the

@@ -33,8 +33,8 @@ phi (test_model_full_scale_real_rows_stay_finite evaluates it). So behind a stag
 complex and at most 0.7072 B (1 + 2^-11); the real ones meet the next stage the same way (its constants for them are again powers
 of w16, or 16 of the 32 directions of w32 with the bound 0.6533), the complex ones keep their magnitude up to the factors above.
 
-M is derived, not tuned on a GPU. The numpy model below (three stages, binary16 constants, one rounding per stage; the layout of
-tensor-fft_amd/csrc/k4096.hpp) is held to it: finite at |x| = M for tones, whose stages all add in phase, and for the corner
+M is derived, not tuned on a GPU. The numpy model of tests/stage_model.py (three stages, binary16 constants, one rounding per stage; the
+layout of tensor-fft_amd/csrc/k4096.hpp) is held to it: finite at |x| = M for tones, whose stages all add in phase, and for the corner
 signals at A_PAIR, finite for full-scale real rows, and NOT finite for the corner signals at A = 65504, the one place in the
 repository where that input is computed: no GPU test feeds it.
 """
@@ -46,6 +46,7 @@ import conv_ref
 import elementwise_bound as eb
 import range_ref as rr
 import sconv_ref as sr
+from stage_model import F1, G2, H3, TW, _I, _c16, _cexp, _stages, stage_model     # noqa: F401
 
 N = rr.N
 
@@ -146,45 +147,7 @@ def test_the_yardstick_product_keeps_subnormals():
     assert float(product(h(2.0 ** -24), h(1024.0))) == 2.0 ** -14
 
 
-# ---- the numpy model of the forward transform at N = 4096
-
-def _cexp(num, den):
-    a = -2.0 * np.pi * (np.asarray(num) % den) / den
-    return np.cos(a) + 1j * np.sin(a)
-
-
-def _c16(z):
-    """component by component to binary16 (through fp32, as the kernels convert their accumulators), back as complex128"""
-    with np.errstate(over="ignore"):
-        return (z.real.astype(np.float32).astype(np.float16).astype(np.float64)
-                + 1j * z.imag.astype(np.float32).astype(np.float16).astype(np.float64))
-
-
-_I = np.arange(16)
-F1 = _c16(_cexp(_I[:, None] * _I[None, :], 16) / 16)                                          # [n2][k0]
-G2 = _c16(_cexp(_I[None, :, None] * (_I[:, None, None] + 16 * _I[None, None, :]), 256) / 16)  # [k0][n1][k1]
-TW = _cexp(_I[:, None] * _I[None, :], 256).astype(np.complex64).astype(np.complex128)         # [n0][k1], fp32
-H3 = _c16(_cexp(_I[None, :, None] * (_I[:, None, None] + 256 * _I[None, None, :]), 4096) / 16)  # [k0][n0][k2]
-
-
-def stage_model(re, im):
-    """DFT(x) / 4096 by three 1/16-scaled radix-16 stages with binary16 constants and one rounding to binary16 behind each
-    (n = n0 + 16 n1 + 256 n2, k = k0 + 16 k1 + 256 k2; stage 1 contracts n2, stage 2 n1 with the fp32 twiddle w256^(n0 k1) on its
-    accumulators, stage 3 n0). Returns (the spectrum as complex128 in natural order, [the largest |component| in front of each
-    stage's rounding])."""
-    x = (np.asarray(re, np.float16).astype(np.float64) + 1j * np.asarray(im, np.float16).astype(np.float64)).reshape(16, 16, 16)   # [n2][n1][n0]
-    a1 = np.einsum("ak,abc->kbc", F1, x)                                  # [k0][n1][n0]
-    a2 = np.einsum("kbj,kbc->kjc", G2, _c16(a1)) * TW.T[None, :, :]       # [k0][k1][n0]
-    a3 = np.einsum("kcm,kjc->kjm", H3, _c16(a2))                          # [k0][k1][k2]
-    peaks = [float(max(np.abs(a.real).max(), np.abs(a.imag).max())) for a in (a1, a2, a3)]
-    return _c16(a3).transpose(2, 1, 0).reshape(N), peaks
-
-
-def _stages(x, round_last):
-    a1 = np.einsum("ak,abc->kbc", F1, x.reshape(16, 16, 16))
-    a2 = np.einsum("kbj,kbc->kjc", G2, _c16(a1)) * TW.T[None, :, :]
-    a3 = np.einsum("kcm,kjc->kjm", H3, _c16(a2)).astype(np.complex64).astype(np.complex128).transpose(2, 1, 0).reshape(N)
-    return _c16(a3) if round_last else a3
+# ---- the numpy model of the forward transform at N = 4096 (tests/stage_model.py, which also models the other single-pass kernels)
 
 
 def fused_route_model(re, im, h):
