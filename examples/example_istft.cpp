@@ -1,0 +1,116 @@
+// example_istft.cpp — filtering in the STFT domain through the C ABI of the STFT add-on and its inverse (include/tfft_stft.h,
+// include/tfft_istft.h): a two-tone signal goes through STFT (Hann window, hop 1024, pad 2048: torch's center=True), the bins of one
+// tone are set to zero, and ISTFT brings the rest back. The ISTFT plan reads the buffer the STFT plan wrote, as it is: no repacking,
+// no gain, no overlap-add and no envelope division in the caller's code.
+//
+// Printed: the amplitude of the removed tone that is left in the result, and the worst error on the kept tone, both over the samples
+// that lie under full frames only (a frame that hangs over the signal's ends sees the tones switched on or off, which is not a
+// line in its spectrum). exit 0 / 1.
+//
+// usage: example_istft [length = 32768]
+#include <hip/hip_fp16.h>
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "tfft_istft.h"
+#include "tfft_stft.h"
+
+#define CHECK_HIP(c)                                                         \
+  do {                                                                       \
+    hipError_t e_ = (c);                                                     \
+    if (e_ != hipSuccess) {                                                  \
+      std::printf("%s: %s\n", #c, hipGetErrorString(e_));                    \
+      return 1;                                                              \
+    }                                                                        \
+  } while (0)
+#define CHECK_TFFT(c, last_error)                                            \
+  do {                                                                       \
+    if ((c) != TFFT_OK) {                                                    \
+      std::printf("%s: %s\n", #c, last_error());                             \
+      return 1;                                                              \
+    }                                                                        \
+  } while (0)
+
+int main(int argc, char** argv) {
+  const unsigned long long L = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 32768;
+  const unsigned long long n = TFFT_STFT_N, hop = 1024, pad = 2048, pitch = TFFT_STFT_PITCH;
+  if (L < 3 * n || L % 8 || L > (1ull << 22)) {
+    std::printf("length must be a multiple of 8 in 12288 .. 2^22\n");
+    return 1;
+  }
+  const int keep = 200, drop = 900;              // the two tones, in bins of the frame length
+  const double amp = 0.3;
+  int dev = 0;
+  CHECK_HIP(hipGetDevice(&dev));
+
+  char text[128];
+  uint64_t frames = 0;
+  CHECK_TFFT(tfft_istft_geometry(L, hop, pad, &frames), tfft_istft_last_error);
+  CHECK_TFFT(tfft_istft_describe(L, hop, pad, 1, 0, text, sizeof(text)), tfft_istft_last_error);
+  tfft_stft_plan* fwd = nullptr;
+  tfft_istft_plan* inv = nullptr;
+  CHECK_TFFT(tfft_stft_plan_create(1, L, hop, pad, dev, nullptr, &fwd), tfft_stft_last_error);
+  CHECK_TFFT(tfft_istft_plan_create(1, L, hop, pad, dev, nullptr, &inv), tfft_istft_last_error);
+  std::printf("L = %llu, hop = %llu, pad = %llu: %llu frames: %s, %d launches, workspace %zu bytes\n", L, hop, pad,
+              static_cast<unsigned long long>(frames), text, tfft_istft_plan_num_launches(inv), tfft_istft_plan_workspace_bytes(inv));
+
+  std::vector<__half> sig(L), win(n);
+  for (unsigned long long t = 0; t < L; ++t) {
+    const double ph = 2.0 * M_PI * static_cast<double>(t) / static_cast<double>(n);
+    sig[t] = __float2half(static_cast<float>(amp * std::cos(keep * ph) + amp * std::sin(drop * ph)));
+  }
+  for (unsigned long long j = 0; j < n; ++j)     // the periodic Hann window
+    win[j] = __float2half(static_cast<float>(0.5 - 0.5 * std::cos(2.0 * M_PI * static_cast<double>(j) / static_cast<double>(n))));
+
+  __half *x = nullptr, *w = nullptr, *spec = nullptr, *y = nullptr;
+  const size_t spec_halves = static_cast<size_t>(frames) * 2 * pitch;         // frame g: [RE 2056 | IM 2056]
+  CHECK_HIP(hipMalloc(&x, L * sizeof(__half)));
+  CHECK_HIP(hipMalloc(&w, n * sizeof(__half)));
+  CHECK_HIP(hipMalloc(&spec, spec_halves * sizeof(__half)));
+  CHECK_HIP(hipMalloc(&y, L * sizeof(__half)));
+  CHECK_HIP(hipMemcpy(x, sig.data(), L * sizeof(__half), hipMemcpyHostToDevice));
+  CHECK_HIP(hipMemcpy(w, win.data(), n * sizeof(__half), hipMemcpyHostToDevice));
+  CHECK_TFFT(tfft_stft_plan_set_window(fwd, w, nullptr), tfft_stft_last_error);
+  CHECK_TFFT(tfft_istft_plan_set_window(inv, w, nullptr), tfft_istft_last_error);
+
+  CHECK_TFFT(tfft_stft_exec(fwd, x, spec, spec + pitch, nullptr), tfft_stft_last_error);
+  // the filter: bins drop - 8 .. drop + 8 of both planes of every frame to zero (a Hann-windowed line on a bin occupies three bins)
+  for (unsigned long long f = 0; f < frames; ++f)
+    for (int plane = 0; plane < 2; ++plane)
+      CHECK_HIP(hipMemsetAsync(spec + f * 2 * pitch + plane * pitch + (drop - 8), 0, 17 * sizeof(__half), nullptr));
+  // an ISTFT plan cannot run in place, and says so
+  const bool refused = tfft_istft_exec(inv, spec, spec + pitch, spec, nullptr) == TFFT_ERR_ARG;
+  std::printf("in place: %s\n", refused ? tfft_istft_last_error() : "NOT refused");
+  CHECK_TFFT(tfft_istft_exec(inv, spec, spec + pitch, y, nullptr), tfft_istft_last_error);
+  CHECK_HIP(hipDeviceSynchronize());
+  std::vector<__half> back(L);
+  CHECK_HIP(hipMemcpy(back.data(), y, L * sizeof(__half), hipMemcpyDeviceToHost));
+
+  // over the samples under full frames only: what is left of the removed tone (its amplitude, by projection), and the worst error
+  // on the kept one
+  double pc = 0, ps = 0, worst = 0;
+  const unsigned long long t0 = n, t1 = L - n;
+  for (unsigned long long t = t0; t < t1; ++t) {
+    const double ph = 2.0 * M_PI * static_cast<double>(t) / static_cast<double>(n);
+    const double e = static_cast<double>(__half2float(back[t])) - amp * std::cos(keep * ph);
+    worst = std::fmax(worst, std::fabs(e));
+    pc += e * std::cos(drop * ph);
+    ps += e * std::sin(drop * ph);
+  }
+  const double left = 2.0 * std::sqrt(pc * pc + ps * ps) / static_cast<double>(t1 - t0);
+  std::printf("removed tone (amplitude %.2f): %.2e left; kept tone (amplitude %.2f): worst error %.2e\n", amp, left, amp, worst);
+  tfft_stft_plan_destroy(fwd);
+  tfft_istft_plan_destroy(inv);
+  (void)hipFree(x);
+  (void)hipFree(w);
+  (void)hipFree(spec);
+  (void)hipFree(y);
+  // binary16 carries 11 bits: 1 % of a tone's amplitude for what is left of the removed one, 2 % for the worst sample of the kept one
+  const bool ok = refused && left <= 0.01 * amp && worst <= 0.02 * amp;
+  std::printf(ok ? "OK\n" : "FAILED\n");
+  return ok ? 0 : 1;
+}

@@ -3,7 +3,7 @@
 Import name: ``tensor_fft_amd`` (see ``tensor_fft_amd.py`` at the repository
 root; the directory carries the upstream project's hyphen).
 
-Eleven layers, all thin:
+Twelve layers, all thin:
 
 * :mod:`.capi` — ctypes binding of the C ABI ``include/tfft.h`` in
   ``libtfft.so`` (hand-written HIP, built in-tree by ``__graft_entry__.build``).
@@ -32,6 +32,9 @@ Eleven layers, all thin:
 * :mod:`.stft` — ctypes binding of the short-time Fourier transform add-on ``include/tfft_stft.h`` in ``libtfft_stft.so`` (hopped,
   windowed frames of 4096 samples of long real signals to half spectra in one kernel; layered on ``libtfft_conv.so`` and
   ``libtfft.so``; no fallback).
+* :mod:`.istft` — ctypes binding of the inverse short-time Fourier transform add-on ``include/tfft_istft.h`` in ``libtfft_istft.so``
+  (half spectra of hopped frames back to real signals: a one-pass C2R of every frame and a windowed overlap-add in a fixed order;
+  layered on ``libtfft_conv.so`` and ``libtfft.so``; no fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -65,6 +68,8 @@ from .gcconv import (TfftGatedChunkedConvGradPlan, TfftGatedChunkedConvPlan, dif
                      gcconv_cache_clear, gcconv_describe, gcconv_geometry, gcconv_lib_path, load_gcconv_library)
 from .stft import (StftOpts, TfftStftPlan, load_stft_library, stft, stft_cache_clear, stft_describe, stft_geometry,  # noqa: F401
                    stft_lib_path)
+from .istft import (IstftOpts, TfftIstftPlan, istft, istft_cache_clear, istft_describe, istft_geometry, istft_lib_path,  # noqa: F401
+                    load_istft_library)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -99,6 +104,7 @@ __all__ = [
     "gated_chunked_causal_conv_input_grad", "gated_chunked_causal_conv_tap_grad", "gcconv_cache_clear", "gcconv_describe", "gcconv_geometry",
     "gcconv_lib_path", "load_gcconv_library",
     "StftOpts", "TfftStftPlan", "load_stft_library", "stft", "stft_cache_clear", "stft_describe", "stft_geometry", "stft_lib_path",
+    "IstftOpts", "TfftIstftPlan", "istft", "istft_cache_clear", "istft_describe", "istft_geometry", "istft_lib_path", "load_istft_library",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]
