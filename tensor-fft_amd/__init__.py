@@ -3,7 +3,7 @@
 Import name: ``tensor_fft_amd`` (see ``tensor_fft_amd.py`` at the repository
 root; the directory carries the upstream project's hyphen).
 
-Twelve layers, all thin:
+Thirteen layers, all thin:
 
 * :mod:`.capi` — ctypes binding of the C ABI ``include/tfft.h`` in
   ``libtfft.so`` (hand-written HIP, built in-tree by ``__graft_entry__.build``).
@@ -35,6 +35,9 @@ Twelve layers, all thin:
 * :mod:`.istft` — ctypes binding of the inverse short-time Fourier transform add-on ``include/tfft_istft.h`` in ``libtfft_istft.so``
   (half spectra of hopped frames back to real signals: a one-pass C2R of every frame and a windowed overlap-add in a fixed order;
   layered on ``libtfft_conv.so`` and ``libtfft.so``; no fallback).
+* :mod:`.stftn` — ctypes binding of the short-frame STFT add-on ``include/tfft_stftn.h`` in ``libtfft_stftn.so`` (the plans of
+  :mod:`.stft` at the frame lengths 512, 1024 and 2048, one kernel each; layered on ``libtfft_conv.so`` and ``libtfft.so``; no
+  fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -70,6 +73,8 @@ from .stft import (StftOpts, TfftStftPlan, load_stft_library, stft, stft_cache_c
                    stft_lib_path)
 from .istft import (IstftOpts, TfftIstftPlan, istft, istft_cache_clear, istft_describe, istft_geometry, istft_lib_path,  # noqa: F401
                     load_istft_library)
+from .stftn import (StftNOpts, TfftShortStftPlan, load_stftn_library, short_stft, stftn_cache_clear, stftn_describe,  # noqa: F401
+                    stftn_geometry, stftn_lib_path)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -105,6 +110,8 @@ __all__ = [
     "gcconv_lib_path", "load_gcconv_library",
     "StftOpts", "TfftStftPlan", "load_stft_library", "stft", "stft_cache_clear", "stft_describe", "stft_geometry", "stft_lib_path",
     "IstftOpts", "TfftIstftPlan", "istft", "istft_cache_clear", "istft_describe", "istft_geometry", "istft_lib_path", "load_istft_library",
+    "StftNOpts", "TfftShortStftPlan", "load_stftn_library", "short_stft", "stftn_cache_clear", "stftn_describe", "stftn_geometry",
+    "stftn_lib_path",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]

@@ -191,8 +191,11 @@ def stft_cache_clear():
         _plans.popitem()[1][0].close()
 
 
-def stft(x, window, hop, center=False):
-    """Short-time Fourier transform at frame length 4096: x a CUDA float16 tensor [R, L] (L a multiple of 8), window a CUDA float16
+def stft(x, window, hop, center=False, n_fft=STFT_N):
+    """n_fft = 512, 1024 or 2048: short_stft(x, window, hop, n_fft, center) of tensor_fft_amd.stftn (include/tfft_stftn.h), with
+    n_fft in the place of 4096 below; nothing of this module is touched. Any other n_fft but 4096 is refused.
+
+    Short-time Fourier transform at frame length 4096: x a CUDA float16 tensor [R, L] (L a multiple of 8), window a CUDA float16
     tensor [win_length <= 4096] (a shorter window is zero-padded to 4096 with the window centred, as torch.stft does), hop a
     multiple of 8. center=False frames from sample 0 (torch.stft(center=False)); center=True pads 2048 zeros on both sides
     (torch.stft(center=True, pad_mode="constant")). Returns (re, im), each an [R, F, 2049] view of one new [R, F, 2, 2056] buffer:
@@ -201,6 +204,12 @@ def stft(x, window, hop, center=False):
     call."""
     import torch
 
+    if n_fft != STFT_N:
+        from . import stftn
+
+        if n_fft not in stftn.STFTN_LENGTHS:
+            raise TfftError(5, "stft takes n_fft = 512, 1024, 2048 or 4096")
+        return stftn.short_stft(x, window, hop, n_fft, center)
     if not (_is_cuda_half(x) and _is_cuda_half(window) and x.dim() == 2 and window.dim() == 1 and window.device == x.device):
         raise TfftError(5, "stft takes CUDA float16 tensors x (R, L) and window (win_length) on one device")
     if window.numel() == 0 or window.numel() > STFT_N:
