@@ -27,6 +27,16 @@
  *      INPUT CONDITION: |4096 (A[k] + i B[k])| <= 64512 for every bin, the TFFT_SCALE_SEQUENTIAL bound of include/tfft.h. Beyond it
  *      the result may hold inf / nan. Nothing is refused: the condition is on the data. Spectra of tfft_stft_exec of signals and
  *      windows with |w x| <= 1 satisfy it unless they were amplified afterwards.
+ *      A condition a caller of stft -> istft can check on the products u = w x: A[k] + i B[k] = DFT(u_2i + i u_2i+1)[k] / 4096, so
+ *      |A[k] + i B[k]| <= mean_j |u_2i[j] + i u_2i+1[j]|, and a pair is safe when that mean is <= 64512 / 4096 = 15.75: in particular
+ *      when both frames have rms(u) <= 15.75 / sqrt 2 = 11.1, or mean |u| <= 7.875. (mean |u| <= 11.1 alone is NOT enough: a cosine and
+ *      a sine of the same bin with mean |u| = 11.1 give |4096 (A + i B)| = 71400.) The limit binds far below the forward plan's: under
+ *      a rectangular window with hop 4096 a tone c cos(2 pi k0 t / 4096) passes up to c = 22.27 (A[k0] = B[k0] = c / 2, |4096 (A + i B)| =
+ *      4096 c / sqrt 2), a constant only up to c = 11.13 (A[0] = B[0] = c): a constant of 22 ends in inf. uniform(-1, 1) noise under a
+ *      Hann window passes up to a factor 2^8. On the lower side nothing overflows, but the round trip loses accuracy: below about
+ *      |x| = 2^-6 the spectra DFT(u) / 4096 enter binary16's subnormals (99 % of the halves at |x| = 2^-10), and istft(stft(x)) against
+ *      x degrades from 4.3e-4 to 3.3e-3 at |x| = 2^-10 and 5.2e-2 at 2^-14 (rel-L2, Hann, hop 1024). Subnormals are kept everywhere:
+ *      in the loads, in the conversions around the gain and in the output.
  *   2. inverse transform. tfft_exec_inverse of the default N = 4096 plan (sequential scaling) on Z'. The RE result is frame 2i, the IM
  *      result frame 2i + 1; each is rounded once to binary16 and stored in the workspace at g * 4096 halves.
  *   3. overlap-add. For sample t of signal r, f ascending over the frames that cover t, j = t + pad - f * hop, both sums from +0:

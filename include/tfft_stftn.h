@@ -35,6 +35,13 @@
  * run on the frames u laid out in the order g, and the two agree in every bit. The accuracy is that plan's: per pair, as
  * include/tfft.h states it (a weak frame paired with a strong one carries the strong one's rounding noise).
  *
+ * INPUT CONDITION: |u_2b[j] + i u_2b+1[j]| <= 64512 for every sample j of every pair, the TFFT_SCALE_SEQUENTIAL bound of
+ * include/tfft.h on the complex sample the pair forms. The condition is on the products u, not on x or w alone. Both frames of a pair
+ * may reach 45600 (64512 / sqrt 2) at once. A self-paired last frame counts as its OWN partner, not as a frame beside zeros, so its
+ * limit is 45600 too and not 65504. Beyond the limit the result may hold inf / nan; nothing is refused: the condition is on the data.
+ * Downwards there is no condition: subnormal x, w and u are kept, but spectra DFT(u) / n below 2^-14 are subnormal binary16 numbers
+ * with fewer bits.
+ *
  * Aliasing. The output planes' extents must not meet the input's extent, and the written parts of the two planes must not share
  * a half; anything else is refused (TFFT_ERR_ARG). The window is copied into the plan.
  *
