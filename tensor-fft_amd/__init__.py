@@ -38,6 +38,8 @@ Thirteen layers, all thin:
 * :mod:`.stftn` — ctypes binding of the short-frame STFT add-on ``include/tfft_stftn.h`` in ``libtfft_stftn.so`` (the plans of
   :mod:`.stft` at the frame lengths 512, 1024 and 2048, one kernel each; layered on ``libtfft_conv.so`` and ``libtfft.so``; no
   fallback).
+* :mod:`.istftn` — ctypes binding of the short-frame inverse STFT add-on ``include/tfft_istftn.h`` in ``libtfft_istftn.so`` (the
+  plans of :mod:`.istft` at the frame lengths 512, 1024 and 2048; layered on ``libtfft_conv.so`` and ``libtfft.so``; no fallback).
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -75,6 +77,8 @@ from .istft import (IstftOpts, TfftIstftPlan, istft, istft_cache_clear, istft_de
                     load_istft_library)
 from .stftn import (StftNOpts, TfftShortStftPlan, load_stftn_library, short_stft, stftn_cache_clear, stftn_describe,  # noqa: F401
                     stftn_geometry, stftn_lib_path)
+from .istftn import (IstftNOpts, TfftShortIstftPlan, istftn_cache_clear, istftn_describe, istftn_geometry, istftn_lib_path,  # noqa: F401
+                     load_istftn_library, short_istft)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -112,6 +116,8 @@ __all__ = [
     "IstftOpts", "TfftIstftPlan", "istft", "istft_cache_clear", "istft_describe", "istft_geometry", "istft_lib_path", "load_istft_library",
     "StftNOpts", "TfftShortStftPlan", "load_stftn_library", "short_stft", "stftn_cache_clear", "stftn_describe", "stftn_geometry",
     "stftn_lib_path",
+    "IstftNOpts", "TfftShortIstftPlan", "istftn_cache_clear", "istftn_describe", "istftn_geometry", "istftn_lib_path",
+    "load_istftn_library", "short_istft",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]

@@ -219,8 +219,9 @@ def istft_cache_clear():
         _plans.popitem()[1][0].close()
 
 
-def istft(re, im, window, hop, length, center=False, raw_sum=False):
-    """Inverse short-time Fourier transform at frame length 4096: re, im the CUDA float16 [R, F, 2049] views stft() returns (bins
+def istft(re, im, window, hop, length, center=False, raw_sum=False, n_fft=ISTFT_N):
+    """Inverse short-time Fourier transform at frame length 4096 (n_fft = 512, 1024 or 2048: istftn.short_istft, which takes the
+    same arguments at that frame length): re, im the CUDA float16 [R, F, 2049] views stft() returns (bins
     0 .. 2048 of rfft(window * frame) / 4096, frame-major), taken as they are; any other [R, F, 2049] pair is copied into that
     layout first. window a CUDA float16 tensor [win_length <= 4096] (a shorter one is zero-padded to 4096 with the window centred, as
     in stft), hop a multiple of 8, length the samples per signal (F must be the frame count of that length). center as in stft.
@@ -229,6 +230,12 @@ def istft(re, im, window, hop, length, center=False, raw_sum=False):
     _version) of it changed since the last call."""
     import torch
 
+    if n_fft != ISTFT_N:
+        from . import istftn
+
+        if n_fft not in istftn.ISTFTN_LENGTHS:
+            raise TfftError(5, "istft takes n_fft = 512, 1024, 2048 or 4096")
+        return istftn.short_istft(re, im, window, hop, length, n_fft, center, raw_sum)
     if not (_is_cuda_half(re) and _is_cuda_half(im) and _is_cuda_half(window) and re.dim() == 3 and re.shape == im.shape
             and re.shape[2] == ISTFT_BINS and window.dim() == 1 and window.device == re.device == im.device):
         raise TfftError(5, "istft takes CUDA float16 tensors re, im (R, F, 2049) and window (win_length) on one device")
