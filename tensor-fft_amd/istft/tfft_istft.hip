@@ -2,63 +2,17 @@
 //
 // Layered on libtfft_conv.so and libtfft.so through their public headers only (status codes, tfft_device_check,
 // tfft_abi_version); from csrc/ it takes k4096.hpp and rsplit.hpp, header only, for the device helpers and the constant tables of
-// the frames kernel (the add-on uploads a copy of its own). The error string, the HIP check, the ABI check, the launch_iters rule, the
-// launch shape and the workspace rules come from conv/host_plumbing.hpp; tests/test_gpu_istft.py holds the frames to
-// tfft_exec_inverse and the output to the numpy overlap-add, bit for bit.
+// the frames kernel (the add-on uploads a copy of its own). Every refusal, the plan-create sequence, the window, the checks of an
+// execution and the grid of the overlap-add come from conv/stft_host.hpp, which the four STFT libraries share, and the workspace
+// rules from conv/host_plumbing.hpp; here are the plan struct, the frames kernel's LDS opt-in, the two launches and the two texts.
+// tests/test_gpu_istft.py holds the frames to tfft_exec_inverse and the output to the numpy overlap-add, bit for bit.
 #include "../../include/tfft_istft.h"
 #include "istft4096.hpp"
 #include "ola.hpp"
-#include "../conv/host_plumbing.hpp"
-
-namespace {
-
-static_assert(TFFT_ISTFT_N == kN, "include/tfft_istft.h and conv/host_math.hpp disagree on the frame length");
-constexpr uint64_t kBins = TFFT_ISTFT_BINS, kPitch = TFFT_ISTFT_PITCH;
-constexpr uint64_t kMaxExtent = uint64_t{1} << 62;       // halves: a byte offset then fits 64 bits
-
-// the frames per signal; `frames` may be null. The refusals of tfft_stft.h
-int check_geometry(uint64_t length, uint64_t hop, uint64_t pad, uint64_t* frames) {
-  if (length < 8 || length % 8) return fail(TFFT_ERR_ARG, "length must be a multiple of 8 and at least 8");
-  if (length > kMaxLength) return fail(TFFT_ERR_ARG, "length must not exceed 2^26");
-  if (hop < 8 || hop % 8) return fail(TFFT_ERR_ARG, "hop must be a multiple of 8 and at least 8");
-  if (pad % 8 || pad >= kN) return fail(TFFT_ERR_ARG, "pad must be a multiple of 8 and below 4096");
-  if (length + 2 * pad < kN) return fail(TFFT_ERR_ARG, "length + 2 * pad must be at least 4096: there is no frame");
-  if (frames) *frames = 1 + (length + 2 * pad - kN) / hop;
-  return TFFT_OK;
-}
-
-int check_shape(uint64_t rows, uint64_t length, uint64_t hop, uint64_t pad, int flags, uint64_t* frames) {
-  uint64_t f = 0;
-  const int rc = check_geometry(length, hop, pad, &f);
-  if (rc) return rc;
-  if (flags & ~TFFT_ISTFT_RAW_SUM)
-    return fail(TFFT_ERR_ARG, "unknown flag bits (" + std::to_string(flags) + "): tfft_istft_opts.flags must be 0 or TFFT_ISTFT_RAW_SUM");
-  if (rows == 0 || rows > 0xffffffffull) return fail(TFFT_ERR_ARG, "rows must be in [1, 2^32)");
-  // frames <= 2^24 + 1: the product cannot overflow 64 bits. A frame index 2 i + 1 of item i must fit 32 bits
-  if (rows * f > 0xffffffffull) return fail(TFFT_ERR_ARG, "the frame count rows * frames must be below 2^32");
-  if (frames) *frames = f;
-  return TFFT_OK;
-}
-
-// (count - 1) * stride + len below 2^62 halves, without overflow
-bool extent_fits(uint64_t count, uint64_t stride, uint64_t len) { return count == 1 || stride <= (kMaxExtent - len - 1) / (count - 1); }
-
-int check_strides(uint64_t rows, uint64_t length, uint64_t frames, uint64_t in_stride, uint64_t out_stride) {
-  if (in_stride && (in_stride % 8 || in_stride < kBins))
-    return fail(TFFT_ERR_ARG, "in_frame_stride must be 0 or a multiple of 8 that is >= 2049");
-  if (out_stride && (out_stride % 8 || out_stride < length))
-    return fail(TFFT_ERR_ARG, "out_sig_stride must be 0 or a multiple of 8 that is >= length");
-  if (!extent_fits(rows * frames, in_stride ? in_stride : 2 * kPitch, kBins))
-    return fail(TFFT_ERR_ARG, "the input extent (rows * frames - 1) * in_frame_stride + 2049 must be below 2^62 halves");
-  if (!extent_fits(rows, out_stride ? out_stride : length, length))
-    return fail(TFFT_ERR_ARG, "the output extent (rows - 1) * out_sig_stride + length must be below 2^62 halves");
-  return TFFT_OK;
-}
-
-}  // namespace
+#include "../conv/stft_host.hpp"
 
 struct tfft_istft_plan {
-  uint64_t rows = 0, length = 0, hop = 0, pad = 0, frames = 0, total = 0, items = 0, in_stride = 0, out_stride = 0;
+  uint64_t n = 0, rows = 0, length = 0, hop = 0, pad = 0, frames = 0, total = 0, items = 0, in_stride = 0, out_stride = 0;
   uint32_t launch_iters = 0;
   int flags = 0, device = 0, num_cus = 256;
   void* d_tables = nullptr;          // F / twiddle / G / H of k4096::build_tables
@@ -72,12 +26,18 @@ struct tfft_istft_plan {
 
 namespace {
 
-int create_device(tfft_istft_plan* p) {
+static_assert(TFFT_ISTFT_N == kN && TFFT_ISTFT_BINS == bins_of(kN) && TFFT_ISTFT_PITCH == pitch_of(kN),
+              "include/tfft_istft.h and the host headers under conv/ disagree on the frame length");
+constexpr stft_rules kRules = {"istft", true, TFFT_ISTFT_RAW_SUM, "must be 0 or TFFT_ISTFT_RAW_SUM", nullptr};
+
+int create_device(tfft_istft_plan* p, const tfft_istft_opts& o) {
+  p->items = (p->total + 1) / 2;
+  p->flags = o.flags;
+  p->ws_need = static_cast<size_t>(p->total * kN * 2);
   std::vector<uint8_t> blob;
   k4096::build_tables(blob);
-  CONV_HIP(hipMalloc(&p->d_tables, k4096::kOffF1n));
-  CONV_HIP(hipMemcpy(p->d_tables, blob.data(), k4096::kOffF1n, hipMemcpyHostToDevice));
-  CONV_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_window), kN * 2));
+  const int rc = create_device_base(p, blob, k4096::kOffF1n);
+  if (rc) return rc;
   // more than 64 KiB of dynamic LDS: opt in now, so that an execution is a pure launch
   CONV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(istft4096::frames_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, k4096::kLdsBytes));
   return TFFT_OK;
@@ -91,77 +51,32 @@ const char* tfft_istft_last_error(void) { return g_err.c_str(); }
 
 int tfft_istft_geometry(uint64_t length, uint64_t hop, uint64_t pad, uint64_t* frames) {
   g_err.clear();
-  return check_geometry(length, hop, pad, frames);
+  return check_geometry(kN, length, hop, pad, frames);
 }
 
 int tfft_istft_describe(uint64_t length, uint64_t hop, uint64_t pad, uint64_t rows, int flags, char* buf, size_t bytes) {
   g_err.clear();
   if (!buf || bytes == 0) return fail(TFFT_ERR_ARG, "null buffer");
   uint64_t frames = 0;
-  const int rc = check_shape(rows, length, hop, pad, flags, &frames);
+  const int rc = check_shape(kRules, kN, rows, length, hop, pad, flags, &frames);
   if (rc) return rc;
   return copy_text("istft4096:4096 x " + std::to_string(frames) + " + ola", buf, bytes);
 }
 
 int tfft_istft_plan_create(uint64_t rows, uint64_t length, uint64_t hop, uint64_t pad, int device_id, const tfft_istft_opts* opts,
                            tfft_istft_plan** out) {
-  g_err.clear();
-  if (!out) return fail(TFFT_ERR_ARG, "null plan pointer");
-  *out = nullptr;
-  tfft_istft_opts o = TFFT_ISTFT_OPTS_INIT;
-  int rc = take_opts(opts, "tfft_istft_opts", o);
-  if (rc) return rc;
-  uint64_t frames = 0;
-  rc = check_shape(rows, length, hop, pad, o.flags, &frames);
-  if (rc == TFFT_OK) rc = check_strides(rows, length, frames, o.in_frame_stride, o.out_sig_stride);
-  if (rc == TFFT_OK) rc = check_launch_iters(o.launch_iters);
-  if (rc == TFFT_OK) rc = check_abi("libtfft_istft.so");
-  if (rc == TFFT_OK) rc = pass_tfft(tfft_device_check(device_id));
-  if (rc) return rc;
-  int prev = 0;
-  CONV_HIP(hipGetDevice(&prev));
-  CONV_HIP(hipSetDevice(device_id));
-  tfft_istft_plan* p = new tfft_istft_plan;
-  p->rows = rows;
-  p->length = length;
-  p->hop = hop;
-  p->pad = pad;
-  p->frames = frames;
-  p->total = rows * frames;
-  p->items = (p->total + 1) / 2;
-  p->in_stride = o.in_frame_stride ? o.in_frame_stride : 2 * kPitch;
-  p->out_stride = o.out_sig_stride ? o.out_sig_stride : length;
-  p->launch_iters = o.launch_iters;
-  p->flags = o.flags;
-  p->device = device_id;
-  p->ws_need = static_cast<size_t>(p->total * kN * 2);
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) p->num_cus = prop.multiProcessorCount;
-  rc = create_device(p);
-  (void)hipSetDevice(prev);
-  if (rc) return fail_create(p, rc, tfft_istft_plan_destroy);
-  *out = p;
-  return TFFT_OK;
+  return create_plan(kRules, kN, rows, length, hop, pad, device_id, opts, tfft_istft_opts TFFT_ISTFT_OPTS_INIT, &tfft_istft_opts::out_sig_stride,
+                     &tfft_istft_opts::in_frame_stride, out, tfft_istft_plan_destroy, create_device);
 }
 
 void tfft_istft_plan_destroy(tfft_istft_plan* p) {
   if (!p) return;
-  if (p->d_tables) (void)hipFree(p->d_tables);
-  if (p->d_window) (void)hipFree(p->d_window);
+  destroy_device_base(p);
   if (p->ws && p->ws_owned) (void)hipFree(p->ws);
   delete p;
 }
 
-int tfft_istft_plan_set_window(tfft_istft_plan* p, const void* window, void* stream) {
-  g_err.clear();
-  if (!p) return fail(TFFT_ERR_ARG, "null plan");
-  if (!window) return fail(TFFT_ERR_ARG, "null window pointer");
-  const int rc = check_current(p->device);
-  if (rc) return rc;
-  CONV_HIP(hipMemcpyAsync(p->d_window, window, kN * 2, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  p->have_window = true;
-  return TFFT_OK;
-}
+int tfft_istft_plan_set_window(tfft_istft_plan* p, const void* window, void* stream) { return set_window(p, window, stream); }
 
 size_t tfft_istft_plan_workspace_bytes(const tfft_istft_plan* p) { return p ? p->ws_need : 0; }
 
@@ -178,22 +93,8 @@ int tfft_istft_plan_prepare(tfft_istft_plan* p) {
 }
 
 int tfft_istft_exec(const tfft_istft_plan* p, const void* in_re, const void* in_im, void* out, void* stream) {
-  g_err.clear();
-  if (!p) return fail(TFFT_ERR_ARG, "null plan");
-  if (!p->have_window) return fail(TFFT_ERR_ARG, "no window: call tfft_istft_plan_set_window first");
-  if (!in_re || !in_im || !out) return fail(TFFT_ERR_ARG, "null data pointer");
-  if ((reinterpret_cast<uintptr_t>(in_re) | reinterpret_cast<uintptr_t>(in_im) | reinterpret_cast<uintptr_t>(out)) & 15)
-    return fail(TFFT_ERR_ARG, "data pointers must be 16-byte aligned");
-  // whole extents, gaps included (conservative): the inputs are never written, and frames are work items that run in no defined order
-  const uint64_t in_bytes = 2 * ((p->total - 1) * p->in_stride + kBins), out_bytes = 2 * ((p->rows - 1) * p->out_stride + p->length);
-  if (blocks_overlap(out, out_bytes, in_re, in_bytes) || blocks_overlap(out, out_bytes, in_im, in_bytes))
-    return fail(TFFT_ERR_ARG, "output and input overlap (an ISTFT plan cannot run in place)");
-  int rc = check_current(p->device);
-  if (rc == TFFT_OK) rc = ws_ensure(p);
+  const int rc = check_exec_inverse(kRules, p, in_re, in_im, out);
   if (rc) return rc;
-  if (blocks_overlap(p->ws, p->ws_need, out, out_bytes)) return fail(TFFT_ERR_ARG, "the workspace overlaps the output");
-  if (blocks_overlap(p->ws, p->ws_need, in_re, in_bytes) || blocks_overlap(p->ws, p->ws_need, in_im, in_bytes))
-    return fail(TFFT_ERR_ARG, "the workspace overlaps the input");
   hipStream_t s = static_cast<hipStream_t>(stream);
   uint16_t* const frames = static_cast<uint16_t*>(p->ws);
   uint32_t live, grid;
@@ -202,14 +103,8 @@ int tfft_istft_exec(const tfft_istft_plan* p, const void* in_re, const void* in_
                      static_cast<const uint16_t*>(in_im), frames, p->in_stride, static_cast<uint32_t>(p->total), static_cast<uint32_t>(p->items), live,
                      static_cast<const uint8_t*>(p->d_tables));
   CONV_HIP(hipGetLastError());
-  // The kernel's frame range is signed 64-bit arithmetic on hop. With more than one frame per signal (F - 1) * hop <= L + 2 pad - 4096
-  // < 2^27; a plan with ONE frame may have any hop up to 2^64 - 8, and all the kernel needs of it is that no second frame starts
-  // inside the padded signal: such a plan passes L + 2 pad, which is what every hop beyond L + 2 pad - 4096 amounts to
-  const uint64_t ola_hop = p->frames > 1 ? p->hop : p->length + 2 * p->pad;
-  const istft4096::ola_geometry geo = {p->rows, p->length / 8, ola_hop, p->out_stride, static_cast<uint32_t>(p->pad), static_cast<uint32_t>(p->frames)};
-  const uint64_t blocks = (p->rows * (p->length / 8) + istft4096::kOlaBlock - 1) / istft4096::kOlaBlock;
-  const uint32_t ola_grid = static_cast<uint32_t>(std::min<uint64_t>(blocks, static_cast<uint64_t>(p->num_cus) * 32));
-  hipLaunchKernelGGL(istft4096::ola_kernel, dim3(ola_grid), dim3(istft4096::kOlaBlock), 0, s, static_cast<const uint16_t*>(frames),
+  const istft4096::ola_geometry geo = {p->rows, p->length / 8, ola_hop(p), p->out_stride, static_cast<uint32_t>(p->pad), static_cast<uint32_t>(p->frames)};
+  hipLaunchKernelGGL(istft4096::ola_kernel, dim3(ola_grid(p, istft4096::kOlaBlock)), dim3(istft4096::kOlaBlock), 0, s, static_cast<const uint16_t*>(frames),
                      static_cast<const uint16_t*>(p->d_window), static_cast<uint16_t*>(out), geo, (p->flags & TFFT_ISTFT_RAW_SUM) ? 1 : 0);
   CONV_HIP(hipGetLastError());
   return TFFT_OK;

@@ -26,7 +26,7 @@ namespace olan {
 constexpr int kOlaBlock = 256;
 
 // L / 8 chunks per signal; hop in samples, below 2^28: (F - 1) * hop <= L + 2 pad - n for F > 1, and the host passes L + 2 pad for a
-// plan with one frame per signal, whatever its hop (tfft_istftn.hip), so the signed 64-bit frame range below cannot overflow
+// plan with one frame per signal, whatever its hop (ola_hop of conv/stft_host.hpp), so the signed 64-bit frame range below cannot overflow
 struct ola_geometry {
   uint64_t rows, chunks, hop, out_stride;
   uint32_t pad, frames, n;
