@@ -52,6 +52,43 @@ static int check_seqs_overlap() {
   return 0;
 }
 
+// The same test with blocks beyond 2^33 bytes of one allocation (tests/far_layout.py, layout `wide`): the interval arithmetic must
+// neither wrap nor lose the high half of (count - 1) * stride. Addresses are compared, never dereferenced.
+static int check_seqs_overlap_far() {
+  const uint64_t stride = (uint64_t{1} << 31) + 8, count = 3, len = 4104;
+  const uintptr_t base = uintptr_t{0x7f00} << 32;           // where a device allocation may lie
+  auto at = [&](uint64_t half) { return reinterpret_cast<const void*>(base + 2 * static_cast<uintptr_t>(half)); };
+  static_assert(sizeof(uintptr_t) == 8, "the far cases need 64-bit addresses");
+  if (2 * (2 * stride) <= (uint64_t{1} << 33)) return 1;    // block 2 of either set starts beyond 2^33 bytes
+  struct row {
+    uint64_t a_first, sa, la, b_first, sb, lb;
+    bool want;
+    const char* what;
+  };
+  const row rows[] = {
+      {0, stride, len, len + 16, stride, len, false, "interleaved sets whose blocks do not touch"},
+      {0, stride, len, len, stride, len, false, "interleaved sets whose blocks abut"},
+      {len + 16, stride, len, 0, stride, len, false, "interleaved sets, the other way round"},
+      {0, stride, len, len - 1, stride, len, true, "the last half of every block of a is the first of b's, block 2 beyond 2^33 bytes"},
+      {len - 1, stride, len, 0, stride, len, true, "the same, the other way round"},
+      {0, stride, len, stride, stride, len, true, "b starts at a's block 1"},
+      // b shifted by two strides: its blocks 1 and 2 lie beyond a's extent, its block 0 meets a's block 2 alone
+      {0, stride, len, 2 * stride + len - 1, stride, len, true, "b's block 0 shares ONE half with a's block 2, beyond 2^33 bytes"},
+      {0, stride, len, 2 * stride + len, stride, len, false, "b begins where a's block 2 ends"},
+      {0, stride, len, 2 * stride + len - 1, stride + 16, len, true, "unequal strides, overlapping extents"},
+      {0, stride, len, len + 16, stride + 16, len, true, "unequal strides, overlapping extents: conservative"},
+      {0, stride, len, 2 * stride + len, stride + 16, len, false, "unequal strides, disjoint extents"},
+  };
+  for (const row& r : rows) {
+    const bool got = hm::seqs_overlap(at(r.a_first), r.sa, r.la, at(r.b_first), r.sb, r.lb, count);
+    if (got != r.want) {
+      std::printf("seqs_overlap far: %s: got %d, want %d\n", r.what, int(got), int(r.want));
+      return 1;
+    }
+  }
+  return 0;
+}
+
 static int check_half_round_trip() {
   for (uint32_t h = 0; h < 65536; ++h) {
     const uint16_t back = hm::to_half(hm::from_half(static_cast<uint16_t>(h)));
@@ -102,7 +139,7 @@ static int check_filter_slot() {
 }
 
 int main() {
-  if (check_seqs_overlap() || check_half_round_trip() || check_geometry() || check_filter_slot()) return 1;
+  if (check_seqs_overlap() || check_seqs_overlap_far() || check_half_round_trip() || check_geometry() || check_filter_slot()) return 1;
   std::printf("ok\n");
   return 0;
 }
