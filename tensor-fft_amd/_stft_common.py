@@ -1,17 +1,12 @@
 """What the four STFT bindings (stft, istft, stftn, istftn) do the same way: the ctypes prototypes of a library, the owning plan
-wrapper with its tensor checks, the cache of plans with the identity of the window each holds, and the tensor functions on top.
-Private: the public names stay in the four modules. No fallback of any kind."""
+wrapper with its tensor checks, the hand-over of a window to a cached plan by identity, and the tensor functions on top. What is
+not about windows and frames (loading, the return-code check, the handle's life cycle, the workspace calls, the cache) is
+_binding.py's. Private: the public names stay in the four modules. No fallback of any kind."""
 import ctypes
-import os
 
-from . import capi, conv
-from .capi import TfftError
-
-
-def _is_cuda_half(t):
-    import torch
-
-    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float16
+from . import conv
+from ._binding import TfftError, _cache_clear, _cached, _check, _Handle, _is_cuda_half, _Workspace  # noqa: F401
+from ._binding import _load as _load_addon
 
 
 def _u32(n):
@@ -31,12 +26,6 @@ def _pitch(n):
 def _load(path, what, prefix, opts, takes_n, inverse):
     """Loads libtfft.so and libtfft_conv.so, then the add-on at `path` ("the `what` add-on"), and sets the prototypes of its calls
     <prefix>*: with the frame length in front where the library `takes_n`, with the workspace calls where it is an `inverse`."""
-    conv.load_conv_library()     # first: the add-on binds to the two libraries (and the HIP runtime) this process already holds
-    if not os.path.exists(path):
-        raise ImportError(
-            f"{path} is missing: the {what} add-on has not been built. "
-            "Run `python -c 'import __graft_entry__ as g; g.build()'` from the repository root.")
-    L = ctypes.CDLL(path)
     vp, u64, ci, sz = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_size_t
     n = [ctypes.c_uint32] if takes_n else []
     protos = {
@@ -52,15 +41,7 @@ def _load(path, what, prefix, opts, takes_n, inverse):
     }
     if inverse:
         protos.update({"plan_workspace_bytes": (sz, [vp]), "plan_set_workspace": (ci, [vp, vp, sz]), "plan_prepare": (ci, [vp])})
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(L, prefix + name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return L
-
-
-def _check(L, prefix, rc):
-    if rc != capi.TFFT_OK:
-        raise TfftError(rc, getattr(L, prefix + "last_error")().decode())
+    return _load_addon(conv.load_conv_library, path, what, {prefix + name: proto for name, proto in protos.items()})
 
 
 def _geometry(L, prefix, n, length, hop, pad):
@@ -78,45 +59,19 @@ def _describe(L, prefix, n, length, hop, pad, rows, flags):
     return buf.value.decode()
 
 
-class _Plan:
+class _Plan(_Handle):
     """What the four plan wrappers share. A subclass sets _prefix ("tfft_stftn_") and _takes_n, and its __init__ calls _create."""
-    _ws = None       # the workspace tensor an inverse plan keeps alive
 
     def _create(self, L, opts, n, rows, length, hop, pad, device):
-        self._lib = L
-        self._h = ctypes.c_void_p()
         front = [_u32(n)] if self._takes_n else []
-        self._call("plan_create", *front, int(rows), int(length), int(hop), int(pad), int(device), ctypes.byref(opts), ctypes.byref(self._h))
+        self._open(L, getattr(L, self._prefix + "plan_create"), *front, int(rows), int(length), int(hop), int(pad), int(device), ctypes.byref(opts))
         self.n, self.rows, self.length, self.hop, self.pad = int(n), int(rows), int(length), int(hop), int(pad)
         self.device = int(device)
         self.bins, self.pitch = _bins(n), _pitch(n)
         self.frames = _geometry(L, self._prefix, n if self._takes_n else None, length, hop, pad)
 
     def _call(self, name, *args):
-        _check(self._lib, self._prefix, getattr(self._lib, self._prefix + name)(*args))
-
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._h = None
-            getattr(self._lib, self._prefix + "plan_destroy")(h)
-            self._ws = None
-
-    __del__ = close
-
-    @property
-    def num_launches(self):
-        return int(getattr(self._lib, self._prefix + "plan_num_launches")(self._h))
-
-    @property
-    def kernels(self):
-        """<prefix>plan_kernels: the kernels one execution launches, in launch order."""
-        return capi._kernel_lines(getattr(self._lib, self._prefix + "plan_kernels"), self._h)
-
-    def _stream(self, stream):
-        import torch
-
-        return torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
+        self._check(getattr(self._lib, self._prefix + name)(*args))
 
     def set_window(self, w, stream=None):
         """Hands the window over (<prefix>plan_set_window): n halves, copied on the stream; the tensor is not referenced by the plan
@@ -136,10 +91,7 @@ class _Plan:
         import torch
 
         for t in tensors:
-            if not (_is_cuda_half(t) and t.is_contiguous()):
-                raise TfftError(5, "buffers must be contiguous CUDA float16 tensors")
-            if t.device.index != self.device:
-                raise TfftError(5, "tensor on another device than the plan")
+            self._check_kind(t, "buffers")
         for t, need, message in needs:
             if t.numel() < need:
                 raise TfftError(5, message)
@@ -166,27 +118,24 @@ class _ForwardPlan(_Plan):
             (out_re, plane, short), (out_im, plane, short)], stream)
 
 
-class _InversePlan(_Plan):
+class _InversePlan(_Workspace, _Plan):
     def _create(self, L, opts, n, rows, length, hop, pad, device):
         super()._create(L, opts, n, rows, length, hop, pad, device)
         self.in_frame_stride = int(opts.in_frame_stride) or 2 * self.pitch
         self.out_sig_stride = int(opts.out_sig_stride) or self.length
 
     def workspace_bytes(self):
-        return int(getattr(self._lib, self._prefix + "plan_workspace_bytes")(self._h))
+        """the bytes of the time-domain frames (a method here, a property on the convolution plans: both are public)"""
+        return self._workspace_bytes()
 
     def set_workspace(self, tensor):
         """Hands a torch CUDA tensor in as the workspace of the time-domain frames (kept alive by the plan); None returns to a
         workspace of the plan's own."""
         if tensor is None:
             self._call("plan_set_workspace", self._h, None, 0)
+            self._ws = None
         else:
-            self._call("plan_set_workspace", self._h, tensor.data_ptr(), tensor.numel() * tensor.element_size())
-        self._ws = tensor
-
-    def prepare(self):
-        """Allocates the plan's own workspace now (<prefix>plan_prepare): later executions only launch kernels."""
-        self._call("plan_prepare", self._h)
+            super().set_workspace(tensor)
 
     def exec_ptr(self, in_re, in_im, out, stream=0):
         self._call("exec", self._h, in_re, in_im, out, stream)
@@ -201,23 +150,7 @@ class _InversePlan(_Plan):
             (out, (self.rows - 1) * self.out_sig_stride + self.length, "the output buffer is shorter than (rows - 1) * out_sig_stride + length")], stream)
 
 
-# ---- the tensor functions. A module keeps the plans of its last `size` keys in a dict of its own, least recently used first out,
-# each entry [plan, identity of the window it holds]
-def _cached(plans, size, key, make):
-    entry = plans.pop(key, None)
-    if entry is None:
-        entry = [make(), None]
-    plans[key] = entry
-    while len(plans) > size:
-        plans.pop(next(iter(plans)))[0].close()
-    return entry
-
-
-def _cache_clear(plans):
-    while plans:
-        plans.popitem()[1][0].close()
-
-
+# ---- the tensor functions, over _binding._cached: each entry [plan, identity of the window it holds]
 def _hand_window(entry, window):
     """Hands `window` (1 .. n values, checked by the caller) to the plan of a cache entry unless the entry holds it already by
     (data_ptr, _version, numel). A shorter window is zero-padded to n with the window centred, as torch.stft does."""

@@ -1,14 +1,18 @@
 """ctypes binding of include/tfft_cconv.h (libtfft_cconv.so, the carried convolution add-on: the overlap-save causal convolution
 and its gradients on a chunk of a longer sequence, with the history in front of x and the future behind g read in place), and the
-torch.autograd hook over it. No fallback of any kind: torch supplies memory, streams and the autograd graph, nothing else."""
+torch.autograd hook over it. No fallback of any kind: torch supplies memory, streams and the autograd graph, nothing else. What the
+convolution bindings share lives in _conv_common.py, the rules for views and contexts among it."""
 import ctypes
 import os
 
-from . import capi, conv
-from .capi import TfftError
+from . import _binding
+from . import _conv_common as common
+from . import conv
+from ._conv_common import _context, _flat_view, _ptr, _strided
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libtfft_cconv.so"
+_PREFIX = "tfft_cconv_"
 
 # every symbol include/tfft_cconv.h declares (tests check that the library exports exactly these)
 SYMBOLS = [
@@ -42,84 +46,54 @@ def cconv_lib_path():
     return os.path.join(_HERE, _LIB_NAME)
 
 
+def _prototypes():
+    vp, u64, u32, ci, sz = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_size_t
+    pu64 = ctypes.POINTER(u64)
+    return {
+        "tfft_cconv_geometry": (ci, [u64, u64, pu64, pu64, pu64, pu64]),
+        "tfft_cconv_plan_create": (ci, [u64, u64, u64, u64, ci, ctypes.POINTER(CconvOpts), ctypes.POINTER(vp)]),
+        "tfft_cconv_plan_destroy": (None, [vp]),
+        "tfft_cconv_plan_set_taps": (ci, [vp, vp, vp]),
+        "tfft_cconv_plan_spectrum": (ci, [vp, vp, vp]),
+        "tfft_cconv_exec": (ci, [vp, vp, vp, vp, vp]),
+        "tfft_cconv_plan_num_launches": (ci, [vp]),
+        "tfft_cconv_plan_kernels": (ci, [vp, ctypes.c_char_p, sz]),
+        "tfft_cconv_describe": (ci, [u64, u64, u64, u64, ci, ctypes.c_char_p, sz]),
+        "tfft_cconv_grad_geometry": (ci, [u64, u64, u64, u64, u32, pu64, pu64, pu64, pu64, pu64]),
+        "tfft_cconv_grad_create": (ci, [u64, u64, u64, u64, ci, ctypes.POINTER(CconvGradOpts), ctypes.POINTER(vp)]),
+        "tfft_cconv_grad_destroy": (None, [vp]),
+        "tfft_cconv_grad_set_taps": (ci, [vp, vp, vp]),
+        "tfft_cconv_grad_spectrum": (ci, [vp, vp, vp]),
+        "tfft_cconv_grad_workspace_bytes": (sz, [vp]),
+        "tfft_cconv_grad_set_workspace": (ci, [vp, vp, sz]),
+        "tfft_cconv_grad_prepare": (ci, [vp]),
+        "tfft_cconv_grad_exec_input_grad": (ci, [vp, vp, vp, vp, vp]),
+        "tfft_cconv_grad_exec_tap_grad": (ci, [vp, vp, vp, vp, vp, vp]),
+        "tfft_cconv_grad_num_launches": (ci, [vp]),
+        "tfft_cconv_grad_kernels": (ci, [vp, ctypes.c_char_p, sz]),
+        "tfft_cconv_grad_describe": (ci, [u64, u64, u64, u64, u32, ci, ctypes.c_char_p, sz]),
+        "tfft_cconv_last_error": (ctypes.c_char_p, []),
+    }
+
+
 _lib = None
 
 
 def load_cconv_library():
     """Loads libtfft.so and libtfft_conv.so, then libtfft_cconv.so; raises (never falls back) when one has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    conv.load_conv_library()     # first: the add-on binds to the two libraries (and the HIP runtime) this process already holds
-    path = cconv_lib_path()
-    if not os.path.exists(path):
-        raise ImportError(
-            f"{path} is missing: the carried convolution add-on has not been built. "
-            "Run `python -c 'import __graft_entry__ as g; g.build()'` from the repository root.")
-    L = ctypes.CDLL(path)
-    vp, u64, u32, ci, sz = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_size_t
-    pu64 = ctypes.POINTER(u64)
-    L.tfft_cconv_geometry.restype = ci
-    L.tfft_cconv_geometry.argtypes = [u64, u64, pu64, pu64, pu64, pu64]
-    L.tfft_cconv_plan_create.restype = ci
-    L.tfft_cconv_plan_create.argtypes = [u64, u64, u64, u64, ci, ctypes.POINTER(CconvOpts), ctypes.POINTER(vp)]
-    L.tfft_cconv_plan_destroy.restype = None
-    L.tfft_cconv_plan_destroy.argtypes = [vp]
-    L.tfft_cconv_plan_set_taps.restype = ci
-    L.tfft_cconv_plan_set_taps.argtypes = [vp, vp, vp]
-    L.tfft_cconv_plan_spectrum.restype = ci
-    L.tfft_cconv_plan_spectrum.argtypes = [vp, vp, vp]
-    L.tfft_cconv_exec.restype = ci
-    L.tfft_cconv_exec.argtypes = [vp, vp, vp, vp, vp]
-    L.tfft_cconv_plan_num_launches.restype = ci
-    L.tfft_cconv_plan_num_launches.argtypes = [vp]
-    L.tfft_cconv_plan_kernels.restype = ci
-    L.tfft_cconv_plan_kernels.argtypes = [vp, ctypes.c_char_p, sz]
-    L.tfft_cconv_describe.restype = ci
-    L.tfft_cconv_describe.argtypes = [u64, u64, u64, u64, ci, ctypes.c_char_p, sz]
-    L.tfft_cconv_grad_geometry.restype = ci
-    L.tfft_cconv_grad_geometry.argtypes = [u64, u64, u64, u64, u32, pu64, pu64, pu64, pu64, pu64]
-    L.tfft_cconv_grad_create.restype = ci
-    L.tfft_cconv_grad_create.argtypes = [u64, u64, u64, u64, ci, ctypes.POINTER(CconvGradOpts), ctypes.POINTER(vp)]
-    L.tfft_cconv_grad_destroy.restype = None
-    L.tfft_cconv_grad_destroy.argtypes = [vp]
-    L.tfft_cconv_grad_set_taps.restype = ci
-    L.tfft_cconv_grad_set_taps.argtypes = [vp, vp, vp]
-    L.tfft_cconv_grad_spectrum.restype = ci
-    L.tfft_cconv_grad_spectrum.argtypes = [vp, vp, vp]
-    L.tfft_cconv_grad_workspace_bytes.restype = sz
-    L.tfft_cconv_grad_workspace_bytes.argtypes = [vp]
-    L.tfft_cconv_grad_set_workspace.restype = ci
-    L.tfft_cconv_grad_set_workspace.argtypes = [vp, vp, sz]
-    L.tfft_cconv_grad_prepare.restype = ci
-    L.tfft_cconv_grad_prepare.argtypes = [vp]
-    L.tfft_cconv_grad_exec_input_grad.restype = ci
-    L.tfft_cconv_grad_exec_input_grad.argtypes = [vp, vp, vp, vp, vp]
-    L.tfft_cconv_grad_exec_tap_grad.restype = ci
-    L.tfft_cconv_grad_exec_tap_grad.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.tfft_cconv_grad_num_launches.restype = ci
-    L.tfft_cconv_grad_num_launches.argtypes = [vp]
-    L.tfft_cconv_grad_kernels.restype = ci
-    L.tfft_cconv_grad_kernels.argtypes = [vp, ctypes.c_char_p, sz]
-    L.tfft_cconv_grad_describe.restype = ci
-    L.tfft_cconv_grad_describe.argtypes = [u64, u64, u64, u64, u32, ci, ctypes.c_char_p, sz]
-    L.tfft_cconv_last_error.restype = ctypes.c_char_p
-    L.tfft_cconv_last_error.argtypes = []
-    _lib = L
-    return L
-
-
-def _check(rc):
-    if rc != capi.TFFT_OK:
-        raise TfftError(rc, load_cconv_library().tfft_cconv_last_error().decode())
+    if _lib is None:
+        _lib = _binding._load(conv.load_conv_library, cconv_lib_path(), "carried convolution", _prototypes())
+    return _lib
 
 
 def cconv_geometry(length, taps, rows=1, channels=1, partials=0):
     """tfft_cconv_grad_geometry: (halo, hop, segments, P, carry_min): the geometry of sconv_geometry, the partial sums per channel of
     the tap gradient under the cap `partials` (0 = none), and K - 1 rounded up to a multiple of 8, the smallest context that loses
     nothing. Host only."""
+    L = load_cconv_library()
     out = [ctypes.c_uint64() for _ in range(5)]
-    _check(load_cconv_library().tfft_cconv_grad_geometry(int(length), int(taps), int(rows), int(channels), int(partials),
+    _binding._check(L, _PREFIX, L.tfft_cconv_grad_geometry(int(length), int(taps), int(rows), int(channels), int(partials),
                                                          *[ctypes.byref(o) for o in out]))
     return tuple(int(o.value) for o in out)
 
@@ -128,65 +102,22 @@ def cconv_describe(length, taps, rows=1, channels=1, partials=0):
     """(tfft_cconv_describe, tfft_cconv_grad_describe): ("cconv4096:4096 x S", "cconv4096:4096 x S | partials P"). Host only."""
     L = load_cconv_library()
     fwd, grad = ctypes.create_string_buffer(128), ctypes.create_string_buffer(128)
-    _check(L.tfft_cconv_describe(int(length), int(taps), int(rows), int(channels), 0, fwd, len(fwd)))
-    _check(L.tfft_cconv_grad_describe(int(length), int(taps), int(rows), int(channels), int(partials), 0, grad, len(grad)))
+    _binding._check(L, _PREFIX, L.tfft_cconv_describe(int(length), int(taps), int(rows), int(channels), 0, fwd, len(fwd)))
+    _binding._check(L, _PREFIX, L.tfft_cconv_grad_describe(int(length), int(taps), int(rows), int(channels), int(partials), 0, grad, len(grad)))
     return fwd.value.decode(), grad.value.decode()
 
 
-def _is_cuda(t, dtype):
-    import torch
-
-    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype
-
-
-class _PlanBase:
-    def _stream(self, stream):
-        import torch
-
-        return torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
-
-    def _check_taps(self, h):
-        import torch
-
-        if not (_is_cuda(h, torch.float16) and h.is_contiguous() and h.device.index == self.device):
-            raise TfftError(5, "taps must be a contiguous CUDA float16 tensor on the plan's device")
-        if h.numel() < self.channels * self.taps:
-            raise TfftError(5, "the taps tensor is shorter than channels * taps")
-
-    def _check_seqs(self, t, stride, length, what="sequences"):
-        import torch
-
-        if not (_is_cuda(t, torch.float16) and t.is_contiguous()):
-            raise TfftError(5, f"{what} must be contiguous CUDA float16 tensors")
-        if t.device.index != self.device:
-            raise TfftError(5, "tensor on another device than the plan")
-        if t.numel() < (self.rows * self.channels - 1) * stride + length:
-            raise TfftError(5, f"{what}: a tensor is shorter than (rows * channels - 1) * stride + length")
-
-    def _spectrum(self, fn):
-        import torch
-
-        h_re = torch.empty((self.channels, self.n), dtype=torch.float16, device=f"cuda:{self.device}")
-        h_im = torch.empty_like(h_re)
-        with torch.cuda.device(self.device):
-            _check(fn(self._h, h_re.data_ptr(), h_im.data_ptr()))
-        return h_re, h_im
-
-
-class TfftChunkedConvPlan(_PlanBase):
+class TfftChunkedConvPlan(common._Taps, common._SeqPlan):
     """Owning wrapper of tfft_cconv_plan: TfftLongConvPlan on a chunk of a longer sequence. y[b][c][t] = sum_j h[c][j] xe[b][c][t - j],
     xe the input with `history` (a multiple of 8, at most halo) samples of context in front of it, read from a second pointer
     (include/tfft_cconv.h). exec(x, y, hist) with hist = None reads zeros there. The output must not overlap the input or the history;
     the input and the history may be views of one buffer."""
+    _prefix, _names_short = _PREFIX, True
 
     def __init__(self, rows, channels, length, taps, device=0, in_seq_stride=0, out_seq_stride=0, launch_iters=0, history=0, hist_seq_stride=0):
         L = load_cconv_library()
-        self._lib = L
-        self._h = ctypes.c_void_p()
         opts = CconvOpts(ctypes.sizeof(CconvOpts), 0, int(in_seq_stride), int(out_seq_stride), int(launch_iters), 0, int(history), int(hist_seq_stride))
-        _check(L.tfft_cconv_plan_create(int(rows), int(channels), int(length), int(taps), int(device), ctypes.byref(opts), ctypes.byref(self._h)))
-        self.rows, self.channels, self.length, self.taps = int(rows), int(channels), int(length), int(taps)
-        self.device = int(device)
+        self._create(L, L.tfft_cconv_plan_create, rows, channels, length, taps, device, opts)
         self.n = CCONV_N
         self.halo, self.hop, self.segments, _, self.carry_min = cconv_geometry(length, taps, rows, channels)
         self.in_seq_stride = int(in_seq_stride) or self.length
@@ -194,65 +125,34 @@ class TfftChunkedConvPlan(_PlanBase):
         self.history = int(history)
         self.hist_seq_stride = int(hist_seq_stride) or self.history
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._h = None
-            self._lib.tfft_cconv_plan_destroy(h)
-
-    __del__ = close
-
-    @property
-    def num_launches(self):
-        return int(self._lib.tfft_cconv_plan_num_launches(self._h))
-
-    @property
-    def kernels(self):
-        """tfft_cconv_plan_kernels: the kernels one execution launches, in launch order."""
-        return capi._kernel_lines(self._lib.tfft_cconv_plan_kernels, self._h)
-
-    def set_taps(self, h, stream=None):
-        """Hands the taps over (tfft_cconv_plan_set_taps): [channels][taps]; the tensor is not referenced afterwards."""
-        import torch
-
-        self._check_taps(h)
-        with torch.cuda.device(self.device):
-            _check(self._lib.tfft_cconv_plan_set_taps(self._h, h.data_ptr(), self._stream(stream)))
-
-    def spectrum(self):
-        """tfft_cconv_plan_spectrum: (h_re, h_im), two CUDA float16 tensors [channels, 4096]."""
-        return self._spectrum(self._lib.tfft_cconv_plan_spectrum)
-
     def exec_ptr(self, src, hist, dst, stream=0):
-        _check(self._lib.tfft_cconv_exec(self._h, src, hist, dst, stream))
+        self._check(self._lib.tfft_cconv_exec(self._h, src, hist, dst, stream))
 
     def exec(self, x, y, hist=None, stream=None):
         """x, y, hist: flat CUDA float16 tensors, sequence (b, c) at (b * channels + c) * its seq stride; hist = None: zeros."""
         import torch
 
-        self._check_seqs(x, self.in_seq_stride, self.length)
-        self._check_seqs(y, self.out_seq_stride, self.length)
+        self._check_seqs(x, self.in_seq_stride)
+        self._check_seqs(y, self.out_seq_stride)
         if hist is not None:
             self._check_seqs(hist, self.hist_seq_stride, self.history, "histories")
         with torch.cuda.device(self.device):
-            self.exec_ptr(x.data_ptr(), None if hist is None else hist.data_ptr(), y.data_ptr(), self._stream(stream))
+            self.exec_ptr(x.data_ptr(), _ptr(hist), y.data_ptr(), self._stream(stream))
 
 
-class TfftChunkedConvGradPlan(_PlanBase):
+class TfftChunkedConvGradPlan(common._Taps, _binding._Workspace, common._SeqPlan):
     """Owning wrapper of tfft_cconv_grad: TfftLongConvGradPlan on a chunk of a longer sequence. input_grad(g, dx, future) reads
     `future` samples of g behind sample L from a second pointer; tap_grad(x, g, dh, history) reads `history` samples of x in front
-    of sample 0 from one (include/tfft_cconv.h). None reads zeros."""
+    of sample 0 from one (include/tfft_cconv.h). None reads zeros. Only the input gradient needs the taps; the workspace is the tap
+    gradient's; `kernels` lists the input gradient's kernel, then the tap gradient's two."""
+    _prefix, _plan, _names_short = _PREFIX, "grad_", True
 
     def __init__(self, rows, channels, length, taps, device=0, x_seq_stride=0, g_seq_stride=0, dx_seq_stride=0, launch_iters=0, partials=0,
                  history=0, hist_seq_stride=0, future=0, fut_seq_stride=0):
         L = load_cconv_library()
-        self._lib = L
-        self._h = ctypes.c_void_p()
         opts = CconvGradOpts(ctypes.sizeof(CconvGradOpts), 0, int(x_seq_stride), int(g_seq_stride), int(dx_seq_stride), int(launch_iters),
                              int(partials), 0, int(history), int(hist_seq_stride), int(future), int(fut_seq_stride))
-        _check(L.tfft_cconv_grad_create(int(rows), int(channels), int(length), int(taps), int(device), ctypes.byref(opts), ctypes.byref(self._h)))
-        self.rows, self.channels, self.length, self.taps = int(rows), int(channels), int(length), int(taps)
-        self.device = int(device)
+        self._create(L, L.tfft_cconv_grad_create, rows, channels, length, taps, device, opts)
         self.n = CCONV_N
         self.halo, self.hop, self.segments, self.partials, self.carry_min = cconv_geometry(length, taps, rows, channels, partials)
         self.x_seq_stride = int(x_seq_stride) or self.length
@@ -261,153 +161,53 @@ class TfftChunkedConvGradPlan(_PlanBase):
         self.history, self.future = int(history), int(future)
         self.hist_seq_stride = int(hist_seq_stride) or self.history
         self.fut_seq_stride = int(fut_seq_stride) or self.future
-        self._ws = None
-
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._h = None
-            self._lib.tfft_cconv_grad_destroy(h)
-            self._ws = None
-
-    __del__ = close
-
-    @property
-    def num_launches(self):
-        return int(self._lib.tfft_cconv_grad_num_launches(self._h))
-
-    @property
-    def workspace_bytes(self):
-        return int(self._lib.tfft_cconv_grad_workspace_bytes(self._h))
-
-    @property
-    def kernels(self):
-        """tfft_cconv_grad_kernels: the input gradient's kernel, then the tap gradient's two."""
-        return capi._kernel_lines(self._lib.tfft_cconv_grad_kernels, self._h)
-
-    def set_taps(self, h, stream=None):
-        """Hands the taps over (tfft_cconv_grad_set_taps): [channels][taps] float16; only the input gradient needs them."""
-        import torch
-
-        self._check_taps(h)
-        with torch.cuda.device(self.device):
-            _check(self._lib.tfft_cconv_grad_set_taps(self._h, h.data_ptr(), self._stream(stream)))
-
-    def spectrum(self):
-        """tfft_cconv_grad_spectrum: (h_re, h_im), H as two CUDA float16 tensors [channels, 4096] (not conjugated)."""
-        return self._spectrum(self._lib.tfft_cconv_grad_spectrum)
-
-    def set_workspace(self, tensor):
-        """Hands a torch CUDA tensor in as the workspace of the tap gradient (kept alive by the plan)."""
-        _check(self._lib.tfft_cconv_grad_set_workspace(self._h, tensor.data_ptr(), tensor.numel() * tensor.element_size()))
-        self._ws = tensor
-
-    def prepare(self):
-        """Allocates the plan's own workspace now (tfft_cconv_grad_prepare): later tap gradients only launch kernels."""
-        _check(self._lib.tfft_cconv_grad_prepare(self._h))
 
     def input_grad_ptr(self, g, future, dx, stream=0):
-        _check(self._lib.tfft_cconv_grad_exec_input_grad(self._h, g, future, dx, stream))
+        self._check(self._lib.tfft_cconv_grad_exec_input_grad(self._h, g, future, dx, stream))
 
     def tap_grad_ptr(self, x, history, g, dh, stream=0):
-        _check(self._lib.tfft_cconv_grad_exec_tap_grad(self._h, x, history, g, dh, stream))
+        self._check(self._lib.tfft_cconv_grad_exec_tap_grad(self._h, x, history, g, dh, stream))
 
     def input_grad(self, g, dx, future=None, stream=None):
         """g, dx, future: flat CUDA float16 tensors, sequence (b, c) at (b * channels + c) * its seq stride; future = None: zeros."""
         import torch
 
-        self._check_seqs(g, self.g_seq_stride, self.length)
-        self._check_seqs(dx, self.dx_seq_stride, self.length)
+        self._check_seqs(g, self.g_seq_stride)
+        self._check_seqs(dx, self.dx_seq_stride)
         if future is not None:
             self._check_seqs(future, self.fut_seq_stride, self.future, "futures")
         with torch.cuda.device(self.device):
-            self.input_grad_ptr(g.data_ptr(), None if future is None else future.data_ptr(), dx.data_ptr(), self._stream(stream))
+            self.input_grad_ptr(g.data_ptr(), _ptr(future), dx.data_ptr(), self._stream(stream))
 
     def tap_grad(self, x, g, dh, history=None, stream=None):
         """x, g, history: flat CUDA float16 tensors; dh: a contiguous CUDA float32 tensor of channels * taps elements."""
         import torch
 
-        self._check_seqs(x, self.x_seq_stride, self.length)
-        self._check_seqs(g, self.g_seq_stride, self.length)
+        self._check_seqs(x, self.x_seq_stride)
+        self._check_seqs(g, self.g_seq_stride)
         if history is not None:
             self._check_seqs(history, self.hist_seq_stride, self.history, "histories")
-        if not (_is_cuda(dh, torch.float32) and dh.is_contiguous() and dh.device.index == self.device and dh.numel() >= self.channels * self.taps):
-            raise TfftError(5, "the tap gradient must be a contiguous CUDA float32 tensor of channels * taps elements on the plan's device")
+        self._check_grad(dh, self.channels * self.taps, "tap")
         with torch.cuda.device(self.device):
-            self.tap_grad_ptr(x.data_ptr(), None if history is None else history.data_ptr(), g.data_ptr(), dh.data_ptr(), self._stream(stream))
+            self.tap_grad_ptr(x.data_ptr(), _ptr(history), g.data_ptr(), dh.data_ptr(), self._stream(stream))
 
 
 # ---- the convenience functions. They take [B, C, L] VIEWS without copying, which is the point of the add-on: a chunk of a longer
 # buffer (x = buf[..., t0:t0 + L]) and its history (buf[..., t0 - Hn:t0]) go to the plan as two pointers and one sequence stride.
 # A view qualifies when its last dimension is contiguous, its sequences are a multiple of 8 halves >= L apart (batch stride =
-# C x that) and it starts on a 16-byte boundary; anything else is made contiguous first, as long_causal_conv does with every input.
-# The plans of the last CCONV_CACHE_SIZE (shape, strides, context, device) keys are kept, least recently used first out, one cache
-# per operation (a caller who needs only one gradient creates no plan for the other); cconv_cache_clear() releases all three.
+# C x that) and it starts on a 16-byte boundary; anything else is made contiguous first, as long_causal_conv does with every input
+# (_conv_common._strided). The plans of the last CCONV_CACHE_SIZE (shape, strides, context, device) keys are kept, least recently
+# used first out, one cache per operation (a caller who needs only one gradient creates no plan for the other); cconv_cache_clear()
+# releases all three.
 CCONV_CACHE_SIZE = 8
 _fwd_plans = {}
 _dx_plans = {}
 _dh_plans = {}
 
 
-def _strided(t):
-    """(tensor, sequence stride): `t` itself where the plan can read it in place, a contiguous copy otherwise"""
-    rows, channels, length = t.shape
-    ok = (t.stride(2) == 1 or length == 1) and t.data_ptr() % 16 == 0
-    stride = length
-    if ok and rows * channels > 1:
-        stride = t.stride(1) if channels > 1 else t.stride(0)
-        ok = stride >= length and stride % 8 == 0 and (rows == 1 or channels == 1 or t.stride(0) == channels * stride)
-    if not ok:
-        t = t.contiguous()
-        stride = length
-    return t, stride
-
-
-def _context(ctx, like, halo, what):
-    """the context as the plan takes it: (tensor or None, samples, stride). Longer than halo: its inner `halo` samples (no window
-    reaches further), the end of a history, the start of a future."""
-    import torch
-
-    if ctx is None or halo == 0 or ctx.shape[-1] == 0:
-        return None, 0, 0
-    if not (_is_cuda(ctx, torch.float16) and ctx.dim() == 3 and ctx.shape[:2] == like.shape[:2] and ctx.device == like.device):
-        raise TfftError(5, f"{what} must be a CUDA float16 tensor (B, C, n) on the device of the sequences")
-    if ctx.shape[2] % 8:
-        raise TfftError(5, f"{what} must hold a multiple of 8 samples per sequence")
-    if ctx.shape[2] > halo:
-        ctx = ctx[..., -halo:] if what == "history" else ctx[..., :halo]
-    ctx, stride = _strided(ctx)
-    return ctx, ctx.shape[2], stride
-
-
-def _cached(cache, key, make):
-    entry = cache.pop(key, None)
-    if entry is None:
-        entry = [make(), None]
-    cache[key] = entry
-    while len(cache) > CCONV_CACHE_SIZE:
-        cache.pop(next(iter(cache)))[0].close()
-    return entry
-
-
-def _hand_taps(entry, h):
-    """set_taps only when (data_ptr, _version) of h changed since the plan's last call, as long_causal_conv does"""
-    ident = (h.data_ptr(), h._version) if h.is_contiguous() else None
-    if ident is None or entry[1] != ident:
-        entry[0].set_taps(h.contiguous().view(-1))
-        entry[1] = ident
-
-
 def cconv_cache_clear():
     """Destroys the plans the chunked_causal_conv* functions cached."""
-    for cache in (_fwd_plans, _dx_plans, _dh_plans):
-        while cache:
-            cache.popitem()[1][0].close()
-
-
-def _flat(t):
-    """the flat tensor from the first element of a qualifying view to the end of its storage: what the plans' exec methods check"""
-    return t.as_strided((t.untyped_storage().nbytes() // 2 - t.storage_offset(),), (1,))
+    _binding._cache_clear(_fwd_plans, _dx_plans, _dh_plans)
 
 
 def chunked_causal_conv(x, h, history=None):
@@ -416,20 +216,18 @@ def chunked_causal_conv(x, h, history=None):
     Neither x nor history is copied when it is a view the plan can read (see above). Returns y [B, C, L], a new tensor."""
     import torch
 
-    if not (_is_cuda(x, torch.float16) and _is_cuda(h, torch.float16) and x.dim() == 3 and h.dim() == 2 and h.shape[0] == x.shape[1]
-            and h.device == x.device):
-        raise TfftError(5, "chunked_causal_conv takes CUDA float16 tensors x (B, C, L) and h (C, K) on one device")
+    common._check_tap_args("chunked_causal_conv takes CUDA float16 tensors x (B, C, L) and h (C, K) on one device", (x,), (), h)
     rows, channels, length = x.shape
     taps = h.shape[1]
     halo = cconv_geometry(length, taps, rows, channels)[0]
     x, x_stride = _strided(x)
     hist, hn, hist_stride = _context(history, x, halo, "history")
     dev = x.device.index
-    entry = _cached(_fwd_plans, (rows, channels, length, taps, dev, x_stride, hn, hist_stride),
-                    lambda: TfftChunkedConvPlan(rows, channels, length, taps, dev, in_seq_stride=x_stride, history=hn, hist_seq_stride=hist_stride))
-    _hand_taps(entry, h)
+    entry = _binding._cached(_fwd_plans, CCONV_CACHE_SIZE, (rows, channels, length, taps, dev, x_stride, hn, hist_stride),
+                           lambda: TfftChunkedConvPlan(rows, channels, length, taps, dev, in_seq_stride=x_stride, history=hn, hist_seq_stride=hist_stride))
+    common._hand_taps(entry, h)
     y = torch.empty((rows, channels, length), dtype=torch.float16, device=x.device)
-    entry[0].exec(_flat(x), y.view(-1), None if hist is None else _flat(hist))
+    entry[0].exec(_flat_view(x), y.view(-1), _flat_view(hist))
     return y
 
 
@@ -438,20 +236,18 @@ def chunked_causal_conv_input_grad(g, h, future=None):
     [B, C, Fn], Fn a multiple of 8 (more than halo samples: the first halo are used). Returns dx [B, C, L], a new tensor."""
     import torch
 
-    if not (_is_cuda(g, torch.float16) and _is_cuda(h, torch.float16) and g.dim() == 3 and h.dim() == 2 and h.shape[0] == g.shape[1]
-            and h.device == g.device):
-        raise TfftError(5, "chunked_causal_conv_input_grad takes CUDA float16 tensors g (B, C, L) and h (C, K) on one device")
+    common._check_tap_args("chunked_causal_conv_input_grad takes CUDA float16 tensors g (B, C, L) and h (C, K) on one device", (g,), (), h)
     rows, channels, length = g.shape
     taps = h.shape[1]
     halo = cconv_geometry(length, taps, rows, channels)[0]
     g, g_stride = _strided(g)
     fut, fn, fut_stride = _context(future, g, halo, "future")
     dev = g.device.index
-    entry = _cached(_dx_plans, (rows, channels, length, taps, dev, g_stride, fn, fut_stride),
-                    lambda: TfftChunkedConvGradPlan(rows, channels, length, taps, dev, g_seq_stride=g_stride, future=fn, fut_seq_stride=fut_stride))
-    _hand_taps(entry, h)
+    entry = _binding._cached(_dx_plans, CCONV_CACHE_SIZE, (rows, channels, length, taps, dev, g_stride, fn, fut_stride),
+                           lambda: TfftChunkedConvGradPlan(rows, channels, length, taps, dev, g_seq_stride=g_stride, future=fn, fut_seq_stride=fut_stride))
+    common._hand_taps(entry, h)
     dx = torch.empty((rows, channels, length), dtype=torch.float16, device=g.device)
-    entry[0].input_grad(_flat(g), dx.view(-1), None if fut is None else _flat(fut))
+    entry[0].input_grad(_flat_view(g), dx.view(-1), _flat_view(fut))
     return dx
 
 
@@ -460,8 +256,7 @@ def chunked_causal_conv_tap_grad(x, g, taps, history=None):
     float32."""
     import torch
 
-    if not (_is_cuda(x, torch.float16) and _is_cuda(g, torch.float16) and x.dim() == 3 and g.shape == x.shape and g.device == x.device):
-        raise TfftError(5, "chunked_causal_conv_tap_grad takes CUDA float16 tensors x and g of one shape (B, C, L) on one device")
+    common._check_seq_args("chunked_causal_conv_tap_grad takes CUDA float16 tensors x and g of one shape (B, C, L) on one device", (x, g))
     rows, channels, length = x.shape
     taps = int(taps)
     halo = cconv_geometry(length, taps, rows, channels)[0]
@@ -469,11 +264,11 @@ def chunked_causal_conv_tap_grad(x, g, taps, history=None):
     g, g_stride = _strided(g)
     hist, hn, hist_stride = _context(history, x, halo, "history")
     dev = x.device.index
-    entry = _cached(_dh_plans, (rows, channels, length, taps, dev, x_stride, g_stride, hn, hist_stride),
-                    lambda: TfftChunkedConvGradPlan(rows, channels, length, taps, dev, x_seq_stride=x_stride, g_seq_stride=g_stride, history=hn,
-                                                    hist_seq_stride=hist_stride))
+    entry = _binding._cached(_dh_plans, CCONV_CACHE_SIZE, (rows, channels, length, taps, dev, x_stride, g_stride, hn, hist_stride),
+                           lambda: TfftChunkedConvGradPlan(rows, channels, length, taps, dev, x_seq_stride=x_stride, g_seq_stride=g_stride, history=hn,
+                                                           hist_seq_stride=hist_stride))
     dh = torch.empty((channels, taps), dtype=torch.float32, device=x.device)
-    entry[0].tap_grad(_flat(x), _flat(g), dh, None if hist is None else _flat(hist))
+    entry[0].tap_grad(_flat_view(x), _flat_view(g), dh, _flat_view(hist))
     return dh
 
 

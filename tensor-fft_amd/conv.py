@@ -1,12 +1,15 @@
-"""ctypes binding of include/tfft_conv.h (libtfft_conv.so, the FFT convolution add-on). No fallback of any kind."""
+"""ctypes binding of include/tfft_conv.h (libtfft_conv.so, the FFT convolution add-on). No fallback of any kind. Loading, the
+handle's life cycle and the workspace calls are _binding.py's; the plan cache is this module's own (see below)."""
 import ctypes
 import os
 
+from . import _binding
 from . import capi
 from .capi import TfftError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libtfft_conv.so"
+_PREFIX = "tfft_conv_"
 
 # every symbol include/tfft_conv.h declares (tests check that the library exports exactly these)
 SYMBOLS = [
@@ -21,59 +24,40 @@ def conv_lib_path():
     return os.path.join(_HERE, _LIB_NAME)
 
 
+def _prototypes():
+    vp, u64, ci, sz = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_size_t
+    return {
+        "tfft_conv_plan_create": (ci, [u64, u64, u64, ci, u64, u64, ci, ctypes.POINTER(vp)]),
+        "tfft_conv_plan_destroy": (None, [vp]),
+        "tfft_conv_plan_set_filter": (ci, [vp, vp, vp, vp]),
+        "tfft_conv_plan_workspace_bytes": (sz, [vp]),
+        "tfft_conv_plan_set_workspace": (ci, [vp, vp, sz]),
+        "tfft_conv_plan_prepare": (ci, [vp]),
+        "tfft_conv_exec": (ci, [vp, vp, vp, vp, vp, vp]),
+        "tfft_conv_plan_num_launches": (ci, [vp]),
+        "tfft_conv_plan_kernels": (ci, [vp, ctypes.c_char_p, sz]),
+        "tfft_conv_describe": (ci, [u64, u64, u64, ci, ctypes.c_char_p, sz]),
+        "tfft_conv_filter_slot": (u64, [u64, ci, u64]),
+        "tfft_conv_last_error": (ctypes.c_char_p, []),
+    }
+
+
 _lib = None
 
 
 def load_conv_library():
     """Loads libtfft.so, then libtfft_conv.so; raises (never falls back) when either has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    capi.load_library()          # first: the add-on binds to the libtfft.so (and the HIP runtime) this process already holds
-    path = conv_lib_path()
-    if not os.path.exists(path):
-        raise ImportError(
-            f"{path} is missing: the convolution add-on has not been built. "
-            "Run `python -c 'import __graft_entry__ as g; g.build()'` from the repository root.")
-    L = ctypes.CDLL(path)
-    vp, u64, ci, sz = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_size_t
-    L.tfft_conv_plan_create.restype = ci
-    L.tfft_conv_plan_create.argtypes = [u64, u64, u64, ci, u64, u64, ci, ctypes.POINTER(vp)]
-    L.tfft_conv_plan_destroy.restype = None
-    L.tfft_conv_plan_destroy.argtypes = [vp]
-    L.tfft_conv_plan_set_filter.restype = ci
-    L.tfft_conv_plan_set_filter.argtypes = [vp, vp, vp, vp]
-    L.tfft_conv_plan_workspace_bytes.restype = sz
-    L.tfft_conv_plan_workspace_bytes.argtypes = [vp]
-    L.tfft_conv_plan_set_workspace.restype = ci
-    L.tfft_conv_plan_set_workspace.argtypes = [vp, vp, sz]
-    L.tfft_conv_plan_prepare.restype = ci
-    L.tfft_conv_plan_prepare.argtypes = [vp]
-    L.tfft_conv_exec.restype = ci
-    L.tfft_conv_exec.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.tfft_conv_plan_num_launches.restype = ci
-    L.tfft_conv_plan_num_launches.argtypes = [vp]
-    L.tfft_conv_plan_kernels.restype = ci
-    L.tfft_conv_plan_kernels.argtypes = [vp, ctypes.c_char_p, sz]
-    L.tfft_conv_describe.restype = ci
-    L.tfft_conv_describe.argtypes = [u64, u64, u64, ci, ctypes.c_char_p, sz]
-    L.tfft_conv_filter_slot.restype = u64
-    L.tfft_conv_filter_slot.argtypes = [u64, ci, u64]
-    L.tfft_conv_last_error.restype = ctypes.c_char_p
-    L.tfft_conv_last_error.argtypes = []
-    _lib = L
-    return L
-
-
-def _check(rc):
-    if rc != capi.TFFT_OK:
-        raise TfftError(rc, load_conv_library().tfft_conv_last_error().decode())
+    if _lib is None:
+        _lib = _binding._load(capi.load_library, conv_lib_path(), "convolution", _prototypes())
+    return _lib
 
 
 def conv_describe(n, batch=1, filters=1, composed=False):
     """tfft_conv_describe: "conv4096:4096" or "<forward chain> | cmul | <inverse chain>". Host only, no GPU needed."""
+    L = load_conv_library()
     buf = ctypes.create_string_buffer(512)
-    _check(load_conv_library().tfft_conv_describe(int(n), int(batch), int(filters), CONV_COMPOSED if composed else 0, buf, len(buf)))
+    _binding._check(L, _PREFIX, L.tfft_conv_describe(int(n), int(batch), int(filters), CONV_COMPOSED if composed else 0, buf, len(buf)))
     return buf.value.decode()
 
 
@@ -85,86 +69,40 @@ def conv_filter_slot(n, k, composed=False):
     return slot
 
 
-def _is_cuda_half(t):
-    import torch
-
-    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float16
-
-
-class TfftConvPlan:
+class TfftConvPlan(_binding._Handle, _binding._Workspace):
     """Owning wrapper of tfft_conv_plan: y_b = ifft(fft(x_b) * H_(b mod filters)) for `batch` complex fp16 signals of length n
     (numpy conventions; include/tfft_conv.h). Planar data as TfftPlan takes it; set_filter(h_re, h_im) takes two CUDA float16 tensors
     of filters * n halves, natural bin order, before the first exec. n = 4096 runs as one fused kernel unless composed=True."""
+    _prefix = _PREFIX
 
     def __init__(self, n, batch=1, filters=1, device=0, in_batch_stride=0, out_batch_stride=0, composed=False):
         L = load_conv_library()
-        self._lib = L
-        self._h = ctypes.c_void_p()
-        _check(L.tfft_conv_plan_create(int(n), int(batch), int(filters), int(device), int(in_batch_stride), int(out_batch_stride),
-                                       CONV_COMPOSED if composed else 0, ctypes.byref(self._h)))
+        self._open(L, L.tfft_conv_plan_create, int(n), int(batch), int(filters), int(device), int(in_batch_stride), int(out_batch_stride),
+                   CONV_COMPOSED if composed else 0)
         self.n, self.batch, self.filters, self.device, self.composed = int(n), int(batch), int(filters), int(device), bool(composed)
         self.in_batch_stride = int(in_batch_stride) or 2 * self.n
         self.out_batch_stride = int(out_batch_stride) or 2 * self.n
-        self._ws = None
-
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._h = None
-            self._lib.tfft_conv_plan_destroy(h)
-
-    __del__ = close
-
-    @property
-    def num_launches(self):
-        return int(self._lib.tfft_conv_plan_num_launches(self._h))
-
-    @property
-    def workspace_bytes(self):
-        return int(self._lib.tfft_conv_plan_workspace_bytes(self._h))
-
-    @property
-    def kernels(self):
-        """tfft_conv_plan_kernels: the kernels one execution launches, in launch order."""
-        return capi._kernel_lines(self._lib.tfft_conv_plan_kernels, self._h)
-
-    def _stream(self, stream):
-        import torch
-
-        return torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
 
     def set_filter(self, h_re, h_im, stream=None):
         """Hands the filter spectra over (tfft_conv_plan_set_filter); the tensors are not referenced afterwards."""
         import torch
 
         for t in (h_re, h_im):
-            if not (_is_cuda_half(t) and t.is_contiguous() and t.device.index == self.device):
+            if not (_binding._is_cuda_half(t) and t.is_contiguous() and t.device.index == self.device):
                 raise TfftError(5, "filter planes must be contiguous CUDA float16 tensors on the plan's device")
             if t.numel() < self.filters * self.n:
                 raise TfftError(5, "a filter plane is shorter than filters * n")
         with torch.cuda.device(self.device):
-            _check(self._lib.tfft_conv_plan_set_filter(self._h, h_re.data_ptr(), h_im.data_ptr(), self._stream(stream)))
-
-    def set_workspace(self, tensor):
-        """Hands a torch CUDA tensor in as the plan's workspace (kept alive by the plan)."""
-        _check(self._lib.tfft_conv_plan_set_workspace(self._h, tensor.data_ptr(), tensor.numel() * tensor.element_size()))
-        self._ws = tensor
-
-    def prepare(self):
-        """Allocates the plan's own workspace now (tfft_conv_plan_prepare): later executions only launch kernels."""
-        _check(self._lib.tfft_conv_plan_prepare(self._h))
+            self._check(self._lib.tfft_conv_plan_set_filter(self._h, h_re.data_ptr(), h_im.data_ptr(), self._stream(stream)))
 
     def exec_ptr(self, in_re, in_im, out_re, out_im, stream=0):
-        _check(self._lib.tfft_conv_exec(self._h, in_re, in_im, out_re, out_im, stream))
+        self._check(self._lib.tfft_conv_exec(self._h, in_re, in_im, out_re, out_im, stream))
 
     def exec(self, in_re, in_im, out_re, out_im, stream=None):
         import torch
 
         for t in (in_re, in_im, out_re, out_im):
-            if not (_is_cuda_half(t) and t.is_contiguous()):
-                raise TfftError(5, "planes must be contiguous CUDA float16 tensors")
-            if t.device.index != self.device:
-                raise TfftError(5, "tensor on another device than the plan")
+            self._check_kind(t, "planes")
         need_in = (self.batch - 1) * self.in_batch_stride + self.n
         need_out = (self.batch - 1) * self.out_batch_stride + self.n
         if in_re.numel() < need_in or in_im.numel() < need_in or out_re.numel() < need_out or out_im.numel() < need_out:
@@ -175,7 +113,8 @@ class TfftConvPlan:
 
 # fftconv keeps the plans of the last CONV_CACHE_SIZE (n, batch, filters, device) shapes, least recently used first out. A plan holds
 # device memory outside torch's allocator (tables, the filter image, a workspace on the composed path): a caller with many shapes
-# should hold TfftConvPlan objects itself; conv_cache_clear() releases the cached ones.
+# should hold TfftConvPlan objects itself; conv_cache_clear() releases the cached ones. An entry is the bare plan, not the
+# [plan, identity] of the other families (_binding._cached): fftconv sets the filter on every call, so there is no identity to keep.
 CONV_CACHE_SIZE = 8
 _plans = {}
 
@@ -203,7 +142,7 @@ def fftconv(x_re, x_im, h_re, h_im):
     the two planes independently."""
     import torch
 
-    if not all(_is_cuda_half(t) and t.dim() == 2 for t in (x_re, x_im, h_re, h_im)) or x_re.shape != x_im.shape or h_re.shape != h_im.shape \
+    if not all(_binding._is_cuda_half(t) and t.dim() == 2 for t in (x_re, x_im, h_re, h_im)) or x_re.shape != x_im.shape or h_re.shape != h_im.shape \
             or h_re.shape[1] != x_re.shape[1]:
         raise TfftError(5, "fftconv takes CUDA float16 tensors x (batch, n) and h (filters, n), RE and IM of equal shape")
     batch, n = x_re.shape

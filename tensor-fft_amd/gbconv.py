@@ -1,14 +1,17 @@
 """ctypes binding of include/tfft_gbconv.h (libtfft_gbconv.so, the gradients of the gated overlap-save causal convolution), and the
 torch.autograd hook over it and the forward plan of gsconv. No fallback of any kind: torch supplies memory, streams and the autograd
-graph, nothing else."""
+graph, nothing else. What the convolution bindings share lives in _conv_common.py."""
 import ctypes
 import os
 
-from . import capi, conv, gsconv
-from .capi import TfftError
+from . import _binding
+from . import _conv_common as common
+from . import conv, gsconv
+from ._conv_common import _flags, _flat, _ptr
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libtfft_gbconv.so"
+_PREFIX = "tfft_gbconv_"
 
 # every symbol include/tfft_gbconv.h declares (tests check that the library exports exactly these)
 SYMBOLS = [
@@ -33,108 +36,72 @@ def gbconv_lib_path():
     return os.path.join(_HERE, _LIB_NAME)
 
 
+def _prototypes():
+    vp, u64, u32, ci, sz = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_size_t
+    pu64 = ctypes.POINTER(u64)
+    return {
+        "tfft_gbconv_geometry": (ci, [u64, u64, u64, u64, u32, pu64, pu64, pu64, pu64]),
+        "tfft_gbconv_plan_create": (ci, [u64, u64, u64, u64, ci, ctypes.POINTER(GbconvOpts), ctypes.POINTER(vp)]),
+        "tfft_gbconv_plan_destroy": (None, [vp]),
+        "tfft_gbconv_plan_set_taps": (ci, [vp, vp, vp, vp]),
+        "tfft_gbconv_plan_spectrum": (ci, [vp, vp, vp]),
+        "tfft_gbconv_plan_workspace_bytes": (sz, [vp]),
+        "tfft_gbconv_plan_set_workspace": (ci, [vp, vp, sz]),
+        "tfft_gbconv_plan_prepare": (ci, [vp]),
+        "tfft_gbconv_exec_input_grad": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+        "tfft_gbconv_exec_tap_grad": (ci, [vp, vp, vp, vp, vp, vp, vp, vp]),
+        "tfft_gbconv_plan_num_launches": (ci, [vp]),
+        "tfft_gbconv_plan_kernels": (ci, [vp, ctypes.c_char_p, sz]),
+        "tfft_gbconv_describe": (ci, [u64, u64, u64, u64, u32, ci, ctypes.c_char_p, sz]),
+        "tfft_gbconv_last_error": (ctypes.c_char_p, []),
+    }
+
+
 _lib = None
 
 
 def load_gbconv_library():
     """Loads libtfft.so and libtfft_conv.so, then libtfft_gbconv.so; raises (never falls back) when one has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    conv.load_conv_library()     # first: the add-on binds to the two libraries (and the HIP runtime) this process already holds
-    path = gbconv_lib_path()
-    if not os.path.exists(path):
-        raise ImportError(
-            f"{path} is missing: the gated convolution gradient add-on has not been built. "
-            "Run `python -c 'import __graft_entry__ as g; g.build()'` from the repository root.")
-    L = ctypes.CDLL(path)
-    vp, u64, u32, ci, sz = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_size_t
-    pu64 = ctypes.POINTER(u64)
-    L.tfft_gbconv_geometry.restype = ci
-    L.tfft_gbconv_geometry.argtypes = [u64, u64, u64, u64, u32, pu64, pu64, pu64, pu64]
-    L.tfft_gbconv_plan_create.restype = ci
-    L.tfft_gbconv_plan_create.argtypes = [u64, u64, u64, u64, ci, ctypes.POINTER(GbconvOpts), ctypes.POINTER(vp)]
-    L.tfft_gbconv_plan_destroy.restype = None
-    L.tfft_gbconv_plan_destroy.argtypes = [vp]
-    L.tfft_gbconv_plan_set_taps.restype = ci
-    L.tfft_gbconv_plan_set_taps.argtypes = [vp, vp, vp, vp]
-    L.tfft_gbconv_plan_spectrum.restype = ci
-    L.tfft_gbconv_plan_spectrum.argtypes = [vp, vp, vp]
-    L.tfft_gbconv_plan_workspace_bytes.restype = sz
-    L.tfft_gbconv_plan_workspace_bytes.argtypes = [vp]
-    L.tfft_gbconv_plan_set_workspace.restype = ci
-    L.tfft_gbconv_plan_set_workspace.argtypes = [vp, vp, sz]
-    L.tfft_gbconv_plan_prepare.restype = ci
-    L.tfft_gbconv_plan_prepare.argtypes = [vp]
-    L.tfft_gbconv_exec_input_grad.restype = ci
-    L.tfft_gbconv_exec_input_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.tfft_gbconv_exec_tap_grad.restype = ci
-    L.tfft_gbconv_exec_tap_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.tfft_gbconv_plan_num_launches.restype = ci
-    L.tfft_gbconv_plan_num_launches.argtypes = [vp]
-    L.tfft_gbconv_plan_kernels.restype = ci
-    L.tfft_gbconv_plan_kernels.argtypes = [vp, ctypes.c_char_p, sz]
-    L.tfft_gbconv_describe.restype = ci
-    L.tfft_gbconv_describe.argtypes = [u64, u64, u64, u64, u32, ci, ctypes.c_char_p, sz]
-    L.tfft_gbconv_last_error.restype = ctypes.c_char_p
-    L.tfft_gbconv_last_error.argtypes = []
-    _lib = L
-    return L
-
-
-def _check(rc):
-    if rc != capi.TFFT_OK:
-        raise TfftError(rc, load_gbconv_library().tfft_gbconv_last_error().decode())
-
-
-def _flags(pre_gate, post_gate):
-    return (GBCONV_PRE_GATE if pre_gate else 0) | (GBCONV_POST_GATE if post_gate else 0)
+    if _lib is None:
+        _lib = _binding._load(conv.load_conv_library, gbconv_lib_path(), "gated convolution gradient", _prototypes())
+    return _lib
 
 
 def gbconv_geometry(length, taps, rows=1, channels=1, partials=0):
     """tfft_gbconv_geometry: (halo, hop, segments, P): the geometry of sconv_geometry and the partial sums per channel of the tap
     gradient under the cap `partials` (0 = none). Host only."""
+    L = load_gbconv_library()
     out = [ctypes.c_uint64() for _ in range(4)]
-    _check(load_gbconv_library().tfft_gbconv_geometry(int(length), int(taps), int(rows), int(channels), int(partials), *[ctypes.byref(o) for o in out]))
+    _binding._check(L, _PREFIX, L.tfft_gbconv_geometry(int(length), int(taps), int(rows), int(channels), int(partials), *[ctypes.byref(o) for o in out]))
     return tuple(int(o.value) for o in out)
 
 
 def gbconv_describe(length, taps, rows=1, channels=1, partials=0, pre_gate=False, post_gate=False):
     """tfft_gbconv_describe: "gbconv4096:4096[:pre][+post] x S | partials P". Host only, no GPU needed."""
+    L = load_gbconv_library()
     buf = ctypes.create_string_buffer(128)
-    _check(load_gbconv_library().tfft_gbconv_describe(int(length), int(taps), int(rows), int(channels), int(partials), _flags(pre_gate, post_gate),
-                                                      buf, len(buf)))
+    _binding._check(L, _PREFIX, L.tfft_gbconv_describe(int(length), int(taps), int(rows), int(channels), int(partials), _flags(pre_gate, post_gate),
+                                                     buf, len(buf)))
     return buf.value.decode()
 
 
-def _is_cuda(t, dtype):
-    import torch
-
-    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-class TfftGatedLongConvGradPlan:
+class TfftGatedLongConvGradPlan(common._GatedTaps, _binding._Workspace, common._SeqPlan):
     """Owning wrapper of tfft_gbconv_plan: the gradients of TfftGatedLongConvPlan for rows x channels real fp16 sequences of `length`
     samples, `taps` <= 2049 taps and one skip weight per channel (include/tfft_gbconv.h). Which gates the forward operator has is
     fixed at creation. input_grad(gy, dx, ...) needs set_taps(h, skip) first and writes dx and, where asked, dpre; tap_grad(x, gy,
     dh, ...) writes [channels][taps] float32 and, where asked, dskip [channels] float32, and needs no taps. `partials` caps the
     partial sums per channel (0 = the library's default); the tap gradient depends on it through the order of fp32 additions only.
-    The gradient of the post gate is TfftGatedLongConvPlan.exec with gy as its post gate."""
+    The gradient of the post gate is TfftGatedLongConvPlan.exec with gy as its post gate. The workspace is the tap gradient's;
+    `kernels` lists the input gradient's kernel, then the tap gradient's two."""
+    _prefix = _PREFIX
 
     def __init__(self, rows, channels, length, taps, device=0, pre_gate=False, post_gate=False, x_seq_stride=0, pre_seq_stride=0,
                  gy_seq_stride=0, post_seq_stride=0, dx_seq_stride=0, dpre_seq_stride=0, launch_iters=0, partials=0):
         L = load_gbconv_library()
-        self._lib = L
-        self._h = ctypes.c_void_p()
         opts = GbconvOpts(ctypes.sizeof(GbconvOpts), 0, int(x_seq_stride), int(pre_seq_stride), int(gy_seq_stride), int(post_seq_stride),
                           int(dx_seq_stride), int(dpre_seq_stride), int(launch_iters), int(partials), _flags(pre_gate, post_gate))
-        _check(L.tfft_gbconv_plan_create(int(rows), int(channels), int(length), int(taps), int(device), ctypes.byref(opts), ctypes.byref(self._h)))
-        self.rows, self.channels, self.length, self.taps = int(rows), int(channels), int(length), int(taps)
-        self.device = int(device)
+        self._create(L, L.tfft_gbconv_plan_create, rows, channels, length, taps, device, opts)
         self.pre_gate, self.post_gate = bool(pre_gate), bool(post_gate)
         self.n = GBCONV_N
         self.halo, self.hop, self.segments, self.partials = gbconv_geometry(length, taps, rows, channels, partials)
@@ -144,86 +111,12 @@ class TfftGatedLongConvGradPlan:
         self.post_seq_stride = int(post_seq_stride) or self.length
         self.dx_seq_stride = int(dx_seq_stride) or self.length
         self.dpre_seq_stride = int(dpre_seq_stride) or self.length
-        self._ws = None
-
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._h = None
-            self._lib.tfft_gbconv_plan_destroy(h)
-            self._ws = None
-
-    __del__ = close
-
-    @property
-    def num_launches(self):
-        return int(self._lib.tfft_gbconv_plan_num_launches(self._h))
-
-    @property
-    def workspace_bytes(self):
-        return int(self._lib.tfft_gbconv_plan_workspace_bytes(self._h))
-
-    @property
-    def kernels(self):
-        """tfft_gbconv_plan_kernels: the input gradient's kernel, then the tap gradient's two."""
-        return capi._kernel_lines(self._lib.tfft_gbconv_plan_kernels, self._h)
-
-    def _stream(self, stream):
-        import torch
-
-        return torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
-
-    def set_taps(self, h, skip=None, stream=None):
-        """Hands the taps [channels][taps] and the skip weights [channels] (or None) over (tfft_gbconv_plan_set_taps): float16; the
-        tensors are not referenced afterwards."""
-        import torch
-
-        for t, count, what in ((h, self.channels * self.taps, "taps"), (skip, self.channels, "skip")):
-            if t is None and what == "skip":
-                continue
-            if not (_is_cuda(t, torch.float16) and t.is_contiguous() and t.device.index == self.device):
-                raise TfftError(5, f"{what} must be a contiguous CUDA float16 tensor on the plan's device")
-            if t.numel() < count:
-                raise TfftError(5, f"the {what} tensor is shorter than channels{' * taps' if what == 'taps' else ''}")
-        with torch.cuda.device(self.device):
-            _check(self._lib.tfft_gbconv_plan_set_taps(self._h, h.data_ptr(), _ptr(skip), self._stream(stream)))
-
-    def spectrum(self):
-        """tfft_gbconv_plan_spectrum: (h_re, h_im), H' as two CUDA float16 tensors [channels, 4096] (not conjugated)."""
-        import torch
-
-        h_re = torch.empty((self.channels, self.n), dtype=torch.float16, device=f"cuda:{self.device}")
-        h_im = torch.empty_like(h_re)
-        with torch.cuda.device(self.device):
-            _check(self._lib.tfft_gbconv_plan_spectrum(self._h, h_re.data_ptr(), h_im.data_ptr()))
-        return h_re, h_im
-
-    def set_workspace(self, tensor):
-        """Hands a torch CUDA tensor in as the workspace of the tap gradient (kept alive by the plan)."""
-        _check(self._lib.tfft_gbconv_plan_set_workspace(self._h, tensor.data_ptr(), tensor.numel() * tensor.element_size()))
-        self._ws = tensor
-
-    def prepare(self):
-        """Allocates the plan's own workspace now (tfft_gbconv_plan_prepare): later tap gradients only launch kernels."""
-        _check(self._lib.tfft_gbconv_plan_prepare(self._h))
 
     def input_grad_ptr(self, gy, dx, post=None, x=None, pre=None, dpre=None, stream=0):
-        _check(self._lib.tfft_gbconv_exec_input_grad(self._h, gy, post, x, pre, dx, dpre, stream))
+        self._check(self._lib.tfft_gbconv_exec_input_grad(self._h, gy, post, x, pre, dx, dpre, stream))
 
     def tap_grad_ptr(self, x, gy, dh, pre=None, post=None, dskip=None, stream=0):
-        _check(self._lib.tfft_gbconv_exec_tap_grad(self._h, x, pre, gy, post, dh, dskip, stream))
-
-    def _check_seqs(self, t, stride):
-        import torch
-
-        if t is None:
-            return
-        if not (_is_cuda(t, torch.float16) and t.is_contiguous()):
-            raise TfftError(5, "sequences and gates must be contiguous CUDA float16 tensors")
-        if t.device.index != self.device:
-            raise TfftError(5, "tensor on another device than the plan")
-        if t.numel() < (self.rows * self.channels - 1) * stride + self.length:
-            raise TfftError(5, "a tensor is shorter than (rows * channels - 1) * stride + length")
+        self._check(self._lib.tfft_gbconv_exec_tap_grad(self._h, x, pre, gy, post, dh, dskip, stream))
 
     def input_grad(self, gy, dx, post=None, x=None, pre=None, dpre=None, stream=None):
         """gy, dx, post, x, pre, dpre: flat CUDA float16 tensors, sequence (b, c) at (b * channels + c) * the tensor's seq stride; dx
@@ -244,12 +137,9 @@ class TfftGatedLongConvGradPlan:
 
         for t, stride in ((x, self.x_seq_stride), (gy, self.gy_seq_stride), (pre, self.pre_seq_stride), (post, self.post_seq_stride)):
             self._check_seqs(t, stride)
-        for t, count, what in ((dh, self.channels * self.taps, "tap"), (dskip, self.channels, "skip")):
-            if t is None and what == "skip":
-                continue
-            if not (_is_cuda(t, torch.float32) and t.is_contiguous() and t.device.index == self.device and t.numel() >= count):
-                raise TfftError(5, f"the {what} gradient must be a contiguous CUDA float32 tensor of channels"
-                                   f"{' * taps' if what == 'tap' else ''} elements on the plan's device")
+        self._check_grad(dh, self.channels * self.taps, "tap")
+        if dskip is not None:
+            self._check_grad(dskip, self.channels, "skip")
         with torch.cuda.device(self.device):
             self.tap_grad_ptr(x.data_ptr(), gy.data_ptr(), dh.data_ptr(), _ptr(pre), _ptr(post), _ptr(dskip), self._stream(stream))
 
@@ -265,24 +155,13 @@ _dh_plans = {}
 
 def _plan_for(cache, rows, channels, length, taps, device, pre_gate, post_gate):
     key = (int(rows), int(channels), int(length), int(taps), int(device), bool(pre_gate), bool(post_gate))
-    entry = cache.pop(key, None)
-    if entry is None:
-        entry = [TfftGatedLongConvGradPlan(rows, channels, length, taps, device, pre_gate=pre_gate, post_gate=post_gate), None]
-    cache[key] = entry
-    while len(cache) > GBCONV_CACHE_SIZE:
-        cache.pop(next(iter(cache)))[0].close()
-    return entry
+    return _binding._cached(cache, GBCONV_CACHE_SIZE, key,
+                          lambda: TfftGatedLongConvGradPlan(rows, channels, length, taps, device, pre_gate=pre_gate, post_gate=post_gate))
 
 
 def gbconv_cache_clear():
     """Destroys the plans gated_long_causal_conv_input_grad and gated_long_causal_conv_tap_grad cached."""
-    for cache in (_dx_plans, _dh_plans):
-        while cache:
-            cache.popitem()[1][0].close()
-
-
-def _flat(t):
-    return None if t is None else t.contiguous().view(-1)
+    _binding._cache_clear(_dx_plans, _dh_plans)
 
 
 def gated_long_causal_conv_input_grad(gy, h, x=None, pre=None, post=None, skip=None, want_dpre=True):
@@ -292,28 +171,17 @@ def gated_long_causal_conv_input_grad(gy, h, x=None, pre=None, post=None, skip=N
     false. Taps and skip are handed to the cached plan again only when (data_ptr, _version) of h or skip changed since the last call."""
     import torch
 
-    ok = _is_cuda(gy, torch.float16) and _is_cuda(h, torch.float16) and gy.dim() == 3 and h.dim() == 2 and h.shape[0] == gy.shape[1] and h.device == gy.device
-    for t in (x, pre, post):
-        ok = ok and (t is None or (_is_cuda(t, torch.float16) and t.shape == gy.shape and t.device == gy.device))
-    ok = ok and (skip is None or (_is_cuda(skip, torch.float16) and skip.shape == (gy.shape[1],) and skip.device == gy.device))
-    if not ok:
-        raise TfftError(5, "gated_long_causal_conv_input_grad takes CUDA float16 tensors gy, x, pre, post (B, C, L), h (C, K) and skip (C,) on one device")
+    common._check_tap_args("gated_long_causal_conv_input_grad takes CUDA float16 tensors gy, x, pre, post (B, C, L), h (C, K) and skip (C,) on one device",
+                           (gy,), (x, pre, post), h, skip)
     if (pre is None) != (x is None):
-        raise TfftError(5, "gated_long_causal_conv_input_grad takes x exactly when it takes pre")
+        raise _binding.TfftError(5, "gated_long_causal_conv_input_grad takes x exactly when it takes pre")
     rows, channels, length = gy.shape
     entry = _plan_for(_dx_plans, rows, channels, length, h.shape[1], gy.device.index, pre is not None, post is not None)
-    plan = entry[0]
-    # (a non-contiguous tensor is copied per call, and a copy's address and version say nothing about its content)
-    ident = (h.data_ptr(), h._version, None if skip is None else (skip.data_ptr(), skip._version))
-    if not h.is_contiguous() or not (skip is None or skip.is_contiguous()):
-        ident = None
-    if ident is None or entry[1] != ident:
-        plan.set_taps(h.contiguous().view(-1), None if skip is None else skip.contiguous())
-        entry[1] = ident
+    common._hand_taps(entry, h, skip)
     gy = gy.contiguous()
     dx = torch.empty_like(gy)
     dpre = torch.empty_like(gy) if pre is not None and want_dpre else None
-    plan.input_grad(gy.view(-1), dx.view(-1), post=_flat(post), x=_flat(x), pre=_flat(pre), dpre=None if dpre is None else dpre.view(-1))
+    entry[0].input_grad(gy.view(-1), dx.view(-1), post=_flat(post), x=_flat(x), pre=_flat(pre), dpre=None if dpre is None else dpre.view(-1))
     return dx, dpre
 
 
@@ -322,11 +190,8 @@ def gated_long_causal_conv_tap_grad(x, gy, taps, pre=None, post=None):
     [C, taps], and dskip = dh[:, 0] as a tensor of its own [C]. x, gy, pre, post: CUDA float16 tensors [B, C, L]."""
     import torch
 
-    ok = _is_cuda(x, torch.float16) and _is_cuda(gy, torch.float16) and x.dim() == 3 and gy.shape == x.shape and gy.device == x.device
-    for t in (pre, post):
-        ok = ok and (t is None or (_is_cuda(t, torch.float16) and t.shape == x.shape and t.device == x.device))
-    if not ok:
-        raise TfftError(5, "gated_long_causal_conv_tap_grad takes CUDA float16 tensors x, gy, pre and post of one shape (B, C, L) on one device")
+    common._check_seq_args("gated_long_causal_conv_tap_grad takes CUDA float16 tensors x, gy, pre and post of one shape (B, C, L) on one device",
+                           (x, gy), (pre, post))
     rows, channels, length = x.shape
     plan = _plan_for(_dh_plans, rows, channels, length, taps, x.device.index, pre is not None, post is not None)[0]
     dh = torch.empty((channels, int(taps)), dtype=torch.float32, device=x.device)

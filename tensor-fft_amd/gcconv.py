@@ -1,16 +1,21 @@
 """ctypes binding of include/tfft_gcconv.h (libtfft_gcconv.so, the gated carried convolution add-on: the gated overlap-save causal
 convolution and its gradients on a chunk of a longer sequence, with the history in front of x and the pre gate and the future behind
 gy and the post gate read in place), and the torch.autograd hook over it. No fallback of any kind: torch supplies memory, streams
-and the autograd graph, nothing else."""
+and the autograd graph, nothing else. What the convolution bindings share lives in _conv_common.py. The tap gradient's function
+refuses a missing gy with a message of its own, after the shared argument check: kept here."""
 import ctypes
 import os
 
-from . import capi, conv
-from .capi import TfftError
-from .cconv import _context, _flat, _is_cuda, _strided, next_history  # noqa: F401  (next_history serves x and the pre gate alike)
+from . import _binding
+from . import _conv_common as common
+from . import conv
+from ._binding import TfftError
+from ._conv_common import _context, _flags, _flat_view, _ptr, _strided
+from .cconv import next_history  # noqa: F401  (next_history serves x and the pre gate alike)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libtfft_gcconv.so"
+_PREFIX = "tfft_gcconv_"
 
 # every symbol include/tfft_gcconv.h declares (tests check that the library exports exactly these)
 SYMBOLS = [
@@ -48,91 +53,53 @@ def gcconv_lib_path():
     return os.path.join(_HERE, _LIB_NAME)
 
 
+def _prototypes():
+    vp, u64, u32, ci, sz = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_size_t
+    pu64 = ctypes.POINTER(u64)
+    return {
+        "tfft_gcconv_geometry": (ci, [u64, u64, pu64, pu64, pu64, pu64]),
+        "tfft_gcconv_plan_create": (ci, [u64, u64, u64, u64, ci, ctypes.POINTER(GcconvOpts), ctypes.POINTER(vp)]),
+        "tfft_gcconv_plan_destroy": (None, [vp]),
+        "tfft_gcconv_plan_set_taps": (ci, [vp, vp, vp, vp]),
+        "tfft_gcconv_plan_spectrum": (ci, [vp, vp, vp]),
+        "tfft_gcconv_exec": (ci, [vp] * 8),
+        "tfft_gcconv_plan_num_launches": (ci, [vp]),
+        "tfft_gcconv_plan_kernels": (ci, [vp, ctypes.c_char_p, sz]),
+        "tfft_gcconv_describe": (ci, [u64, u64, u64, u64, ci, ctypes.c_char_p, sz]),
+        "tfft_gcconv_grad_geometry": (ci, [u64, u64, u64, u64, u32, pu64, pu64, pu64, pu64, pu64]),
+        "tfft_gcconv_grad_create": (ci, [u64, u64, u64, u64, ci, ctypes.POINTER(GcconvGradOpts), ctypes.POINTER(vp)]),
+        "tfft_gcconv_grad_destroy": (None, [vp]),
+        "tfft_gcconv_grad_set_taps": (ci, [vp, vp, vp, vp]),
+        "tfft_gcconv_grad_spectrum": (ci, [vp, vp, vp]),
+        "tfft_gcconv_grad_workspace_bytes": (sz, [vp]),
+        "tfft_gcconv_grad_set_workspace": (ci, [vp, vp, sz]),
+        "tfft_gcconv_grad_prepare": (ci, [vp]),
+        "tfft_gcconv_grad_exec_input_grad": (ci, [vp] * 10),
+        "tfft_gcconv_grad_exec_tap_grad": (ci, [vp] * 10),
+        "tfft_gcconv_grad_num_launches": (ci, [vp]),
+        "tfft_gcconv_grad_kernels": (ci, [vp, ctypes.c_char_p, sz]),
+        "tfft_gcconv_grad_describe": (ci, [u64, u64, u64, u64, u32, ci, ctypes.c_char_p, sz]),
+        "tfft_gcconv_last_error": (ctypes.c_char_p, []),
+    }
+
+
 _lib = None
 
 
 def load_gcconv_library():
     """Loads libtfft.so and libtfft_conv.so, then libtfft_gcconv.so; raises (never falls back) when one has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    conv.load_conv_library()     # first: the add-on binds to the two libraries (and the HIP runtime) this process already holds
-    path = gcconv_lib_path()
-    if not os.path.exists(path):
-        raise ImportError(
-            f"{path} is missing: the gated carried convolution add-on has not been built. "
-            "Run `python -c 'import __graft_entry__ as g; g.build()'` from the repository root.")
-    L = ctypes.CDLL(path)
-    vp, u64, u32, ci, sz = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_size_t
-    pu64 = ctypes.POINTER(u64)
-    L.tfft_gcconv_geometry.restype = ci
-    L.tfft_gcconv_geometry.argtypes = [u64, u64, pu64, pu64, pu64, pu64]
-    L.tfft_gcconv_plan_create.restype = ci
-    L.tfft_gcconv_plan_create.argtypes = [u64, u64, u64, u64, ci, ctypes.POINTER(GcconvOpts), ctypes.POINTER(vp)]
-    L.tfft_gcconv_plan_destroy.restype = None
-    L.tfft_gcconv_plan_destroy.argtypes = [vp]
-    L.tfft_gcconv_plan_set_taps.restype = ci
-    L.tfft_gcconv_plan_set_taps.argtypes = [vp, vp, vp, vp]
-    L.tfft_gcconv_plan_spectrum.restype = ci
-    L.tfft_gcconv_plan_spectrum.argtypes = [vp, vp, vp]
-    L.tfft_gcconv_exec.restype = ci
-    L.tfft_gcconv_exec.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.tfft_gcconv_plan_num_launches.restype = ci
-    L.tfft_gcconv_plan_num_launches.argtypes = [vp]
-    L.tfft_gcconv_plan_kernels.restype = ci
-    L.tfft_gcconv_plan_kernels.argtypes = [vp, ctypes.c_char_p, sz]
-    L.tfft_gcconv_describe.restype = ci
-    L.tfft_gcconv_describe.argtypes = [u64, u64, u64, u64, ci, ctypes.c_char_p, sz]
-    L.tfft_gcconv_grad_geometry.restype = ci
-    L.tfft_gcconv_grad_geometry.argtypes = [u64, u64, u64, u64, u32, pu64, pu64, pu64, pu64, pu64]
-    L.tfft_gcconv_grad_create.restype = ci
-    L.tfft_gcconv_grad_create.argtypes = [u64, u64, u64, u64, ci, ctypes.POINTER(GcconvGradOpts), ctypes.POINTER(vp)]
-    L.tfft_gcconv_grad_destroy.restype = None
-    L.tfft_gcconv_grad_destroy.argtypes = [vp]
-    L.tfft_gcconv_grad_set_taps.restype = ci
-    L.tfft_gcconv_grad_set_taps.argtypes = [vp, vp, vp, vp]
-    L.tfft_gcconv_grad_spectrum.restype = ci
-    L.tfft_gcconv_grad_spectrum.argtypes = [vp, vp, vp]
-    L.tfft_gcconv_grad_workspace_bytes.restype = sz
-    L.tfft_gcconv_grad_workspace_bytes.argtypes = [vp]
-    L.tfft_gcconv_grad_set_workspace.restype = ci
-    L.tfft_gcconv_grad_set_workspace.argtypes = [vp, vp, sz]
-    L.tfft_gcconv_grad_prepare.restype = ci
-    L.tfft_gcconv_grad_prepare.argtypes = [vp]
-    L.tfft_gcconv_grad_exec_input_grad.restype = ci
-    L.tfft_gcconv_grad_exec_input_grad.argtypes = [vp] * 10
-    L.tfft_gcconv_grad_exec_tap_grad.restype = ci
-    L.tfft_gcconv_grad_exec_tap_grad.argtypes = [vp] * 10
-    L.tfft_gcconv_grad_num_launches.restype = ci
-    L.tfft_gcconv_grad_num_launches.argtypes = [vp]
-    L.tfft_gcconv_grad_kernels.restype = ci
-    L.tfft_gcconv_grad_kernels.argtypes = [vp, ctypes.c_char_p, sz]
-    L.tfft_gcconv_grad_describe.restype = ci
-    L.tfft_gcconv_grad_describe.argtypes = [u64, u64, u64, u64, u32, ci, ctypes.c_char_p, sz]
-    L.tfft_gcconv_last_error.restype = ctypes.c_char_p
-    L.tfft_gcconv_last_error.argtypes = []
-    _lib = L
-    return L
-
-
-def _check(rc):
-    if rc != capi.TFFT_OK:
-        raise TfftError(rc, load_gcconv_library().tfft_gcconv_last_error().decode())
-
-
-def _flags(pre_gate, post_gate):
-    return (GCCONV_PRE_GATE if pre_gate else 0) | (GCCONV_POST_GATE if post_gate else 0)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+    if _lib is None:
+        _lib = _binding._load(conv.load_conv_library, gcconv_lib_path(), "gated carried convolution", _prototypes())
+    return _lib
 
 
 def gcconv_geometry(length, taps, rows=1, channels=1, partials=0):
     """tfft_gcconv_grad_geometry: (halo, hop, segments, P, carry_min), as cconv_geometry. Host only."""
+    L = load_gcconv_library()
     out = [ctypes.c_uint64() for _ in range(5)]
-    _check(load_gcconv_library().tfft_gcconv_grad_geometry(int(length), int(taps), int(rows), int(channels), int(partials),
-                                                           *[ctypes.byref(o) for o in out]))
+    _binding._check(L, _PREFIX, L.tfft_gcconv_grad_geometry(int(length), int(taps), int(rows), int(channels), int(partials),
+                                                          *[ctypes.byref(o) for o in out]))
     return tuple(int(o.value) for o in out)
 
 
@@ -141,65 +108,24 @@ def gcconv_describe(length, taps, rows=1, channels=1, partials=0, pre_gate=False
     Host only."""
     L = load_gcconv_library()
     fwd, grad = ctypes.create_string_buffer(128), ctypes.create_string_buffer(128)
-    _check(L.tfft_gcconv_describe(int(length), int(taps), int(rows), int(channels), _flags(pre_gate, post_gate), fwd, len(fwd)))
-    _check(L.tfft_gcconv_grad_describe(int(length), int(taps), int(rows), int(channels), int(partials), _flags(pre_gate, post_gate), grad, len(grad)))
+    _binding._check(L, _PREFIX, L.tfft_gcconv_describe(int(length), int(taps), int(rows), int(channels), _flags(pre_gate, post_gate), fwd, len(fwd)))
+    _binding._check(L, _PREFIX, L.tfft_gcconv_grad_describe(int(length), int(taps), int(rows), int(channels), int(partials), _flags(pre_gate, post_gate),
+                                                          grad, len(grad)))
     return fwd.value.decode(), grad.value.decode()
 
 
-class _PlanBase:
-    def _stream(self, stream):
-        import torch
-
-        return torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream
-
-    def _check_taps(self, h, skip):
-        import torch
-
-        for t, count, what in ((h, self.channels * self.taps, "taps"), (skip, self.channels, "skip")):
-            if t is None and what == "skip":
-                continue
-            if not (_is_cuda(t, torch.float16) and t.is_contiguous() and t.device.index == self.device):
-                raise TfftError(5, f"{what} must be a contiguous CUDA float16 tensor on the plan's device")
-            if t.numel() < count:
-                raise TfftError(5, f"the {what} tensor is shorter than channels{' * taps' if what == 'taps' else ''}")
-
-    def _check_seqs(self, t, stride, length, what="sequences and gates"):
-        import torch
-
-        if t is None:
-            return
-        if not (_is_cuda(t, torch.float16) and t.is_contiguous()):
-            raise TfftError(5, f"{what} must be contiguous CUDA float16 tensors")
-        if t.device.index != self.device:
-            raise TfftError(5, "tensor on another device than the plan")
-        if t.numel() < (self.rows * self.channels - 1) * stride + length:
-            raise TfftError(5, f"{what}: a tensor is shorter than (rows * channels - 1) * stride + length")
-
-    def _spectrum(self, fn):
-        import torch
-
-        h_re = torch.empty((self.channels, self.n), dtype=torch.float16, device=f"cuda:{self.device}")
-        h_im = torch.empty_like(h_re)
-        with torch.cuda.device(self.device):
-            _check(fn(self._h, h_re.data_ptr(), h_im.data_ptr()))
-        return h_re, h_im
-
-
-class TfftGatedChunkedConvPlan(_PlanBase):
+class TfftGatedChunkedConvPlan(common._GatedTaps, common._SeqPlan):
     """Owning wrapper of tfft_gcconv_plan: TfftGatedLongConvPlan on a chunk of a longer sequence. y = post * (h' * (pe * xe)), xe and pe
     the input and the pre gate with `history` (a multiple of 8, at most halo) samples of context in front of them, each read from a
     second pointer (include/tfft_gcconv.h). exec(x, y, pre, post, hist, pre_hist) with hist = None reads zeros there."""
+    _prefix, _names_short = _PREFIX, True
 
     def __init__(self, rows, channels, length, taps, device=0, pre_gate=False, post_gate=False, in_seq_stride=0, out_seq_stride=0,
                  pre_seq_stride=0, post_seq_stride=0, launch_iters=0, history=0, hist_seq_stride=0, pre_hist_seq_stride=0):
         L = load_gcconv_library()
-        self._lib = L
-        self._h = ctypes.c_void_p()
         opts = GcconvOpts(ctypes.sizeof(GcconvOpts), 0, int(in_seq_stride), int(out_seq_stride), int(pre_seq_stride), int(post_seq_stride),
                           int(launch_iters), _flags(pre_gate, post_gate), int(history), int(hist_seq_stride), int(pre_hist_seq_stride))
-        _check(L.tfft_gcconv_plan_create(int(rows), int(channels), int(length), int(taps), int(device), ctypes.byref(opts), ctypes.byref(self._h)))
-        self.rows, self.channels, self.length, self.taps = int(rows), int(channels), int(length), int(taps)
-        self.device = int(device)
+        self._create(L, L.tfft_gcconv_plan_create, rows, channels, length, taps, device, opts)
         self.pre_gate, self.post_gate = bool(pre_gate), bool(post_gate)
         self.n = GCCONV_N
         self.halo, self.hop, self.segments, _, self.carry_min = gcconv_geometry(length, taps, rows, channels)
@@ -211,37 +137,8 @@ class TfftGatedChunkedConvPlan(_PlanBase):
         self.hist_seq_stride = int(hist_seq_stride) or self.history
         self.pre_hist_seq_stride = int(pre_hist_seq_stride) or self.history
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._h = None
-            self._lib.tfft_gcconv_plan_destroy(h)
-
-    __del__ = close
-
-    @property
-    def num_launches(self):
-        return int(self._lib.tfft_gcconv_plan_num_launches(self._h))
-
-    @property
-    def kernels(self):
-        """tfft_gcconv_plan_kernels: the kernels one execution launches, in launch order."""
-        return capi._kernel_lines(self._lib.tfft_gcconv_plan_kernels, self._h)
-
-    def set_taps(self, h, skip=None, stream=None):
-        """Hands the taps [channels][taps] and the skip weights [channels] (or None) over (tfft_gcconv_plan_set_taps)."""
-        import torch
-
-        self._check_taps(h, skip)
-        with torch.cuda.device(self.device):
-            _check(self._lib.tfft_gcconv_plan_set_taps(self._h, h.data_ptr(), _ptr(skip), self._stream(stream)))
-
-    def spectrum(self):
-        """tfft_gcconv_plan_spectrum: (h_re, h_im), two CUDA float16 tensors [channels, 4096]."""
-        return self._spectrum(self._lib.tfft_gcconv_plan_spectrum)
-
     def exec_ptr(self, src, dst, pre=None, post=None, hist=None, pre_hist=None, stream=0):
-        _check(self._lib.tfft_gcconv_exec(self._h, src, pre, post, hist, pre_hist, dst, stream))
+        self._check(self._lib.tfft_gcconv_exec(self._h, src, pre, post, hist, pre_hist, dst, stream))
 
     def exec(self, x, y, pre=None, post=None, hist=None, pre_hist=None, stream=None):
         """x, y, pre, post, hist, pre_hist: flat CUDA float16 tensors, sequence (b, c) at (b * channels + c) * its seq stride; hist = None:
@@ -249,31 +146,29 @@ class TfftGatedChunkedConvPlan(_PlanBase):
         import torch
 
         for t, stride in ((x, self.in_seq_stride), (y, self.out_seq_stride), (pre, self.pre_seq_stride), (post, self.post_seq_stride)):
-            self._check_seqs(t, stride, self.length)
+            self._check_seqs(t, stride)
         self._check_seqs(hist, self.hist_seq_stride, self.history, "histories")
         self._check_seqs(pre_hist, self.pre_hist_seq_stride, self.history, "histories")
         with torch.cuda.device(self.device):
             self.exec_ptr(x.data_ptr(), y.data_ptr(), _ptr(pre), _ptr(post), _ptr(hist), _ptr(pre_hist), self._stream(stream))
 
 
-class TfftGatedChunkedConvGradPlan(_PlanBase):
+class TfftGatedChunkedConvGradPlan(common._GatedTaps, _binding._Workspace, common._SeqPlan):
     """Owning wrapper of tfft_gcconv_grad: TfftGatedLongConvGradPlan on a chunk of a longer sequence. input_grad reads `future` samples
     of gy and of the post gate behind sample L, tap_grad reads `history` samples of x and of the pre gate in front of sample 0, each
-    from a pointer of its own (include/tfft_gcconv.h). None reads zeros."""
+    from a pointer of its own (include/tfft_gcconv.h). None reads zeros. Only the input gradient needs the taps; the workspace is
+    the tap gradient's; `kernels` lists the input gradient's kernel, then the tap gradient's two."""
+    _prefix, _plan, _names_short = _PREFIX, "grad_", True
 
     def __init__(self, rows, channels, length, taps, device=0, pre_gate=False, post_gate=False, x_seq_stride=0, pre_seq_stride=0,
                  gy_seq_stride=0, post_seq_stride=0, dx_seq_stride=0, dpre_seq_stride=0, launch_iters=0, partials=0, history=0,
                  hist_seq_stride=0, pre_hist_seq_stride=0, future=0, fut_seq_stride=0, post_fut_seq_stride=0):
         L = load_gcconv_library()
-        self._lib = L
-        self._h = ctypes.c_void_p()
         opts = GcconvGradOpts(ctypes.sizeof(GcconvGradOpts), 0, int(x_seq_stride), int(pre_seq_stride), int(gy_seq_stride), int(post_seq_stride),
                               int(dx_seq_stride), int(dpre_seq_stride), int(launch_iters), int(partials), _flags(pre_gate, post_gate),
                               int(history), int(hist_seq_stride), int(pre_hist_seq_stride), int(future), int(fut_seq_stride),
                               int(post_fut_seq_stride))
-        _check(L.tfft_gcconv_grad_create(int(rows), int(channels), int(length), int(taps), int(device), ctypes.byref(opts), ctypes.byref(self._h)))
-        self.rows, self.channels, self.length, self.taps = int(rows), int(channels), int(length), int(taps)
-        self.device = int(device)
+        self._create(L, L.tfft_gcconv_grad_create, rows, channels, length, taps, device, opts)
         self.pre_gate, self.post_gate = bool(pre_gate), bool(post_gate)
         self.n = GCCONV_N
         self.halo, self.hop, self.segments, self.partials, self.carry_min = gcconv_geometry(length, taps, rows, channels, partials)
@@ -288,56 +183,12 @@ class TfftGatedChunkedConvGradPlan(_PlanBase):
         self.pre_hist_seq_stride = int(pre_hist_seq_stride) or self.history
         self.fut_seq_stride = int(fut_seq_stride) or self.future
         self.post_fut_seq_stride = int(post_fut_seq_stride) or self.future
-        self._ws = None
-
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._h = None
-            self._lib.tfft_gcconv_grad_destroy(h)
-            self._ws = None
-
-    __del__ = close
-
-    @property
-    def num_launches(self):
-        return int(self._lib.tfft_gcconv_grad_num_launches(self._h))
-
-    @property
-    def workspace_bytes(self):
-        return int(self._lib.tfft_gcconv_grad_workspace_bytes(self._h))
-
-    @property
-    def kernels(self):
-        """tfft_gcconv_grad_kernels: the input gradient's kernel, then the tap gradient's two."""
-        return capi._kernel_lines(self._lib.tfft_gcconv_grad_kernels, self._h)
-
-    def set_taps(self, h, skip=None, stream=None):
-        """Hands the taps and the skip weights over (tfft_gcconv_grad_set_taps); only the input gradient needs them."""
-        import torch
-
-        self._check_taps(h, skip)
-        with torch.cuda.device(self.device):
-            _check(self._lib.tfft_gcconv_grad_set_taps(self._h, h.data_ptr(), _ptr(skip), self._stream(stream)))
-
-    def spectrum(self):
-        """tfft_gcconv_grad_spectrum: (h_re, h_im), H' as two CUDA float16 tensors [channels, 4096] (not conjugated)."""
-        return self._spectrum(self._lib.tfft_gcconv_grad_spectrum)
-
-    def set_workspace(self, tensor):
-        """Hands a torch CUDA tensor in as the workspace of the tap gradient (kept alive by the plan)."""
-        _check(self._lib.tfft_gcconv_grad_set_workspace(self._h, tensor.data_ptr(), tensor.numel() * tensor.element_size()))
-        self._ws = tensor
-
-    def prepare(self):
-        """Allocates the plan's own workspace now (tfft_gcconv_grad_prepare): later tap gradients only launch kernels."""
-        _check(self._lib.tfft_gcconv_grad_prepare(self._h))
 
     def input_grad_ptr(self, gy, dx, post=None, x=None, pre=None, dpre=None, future=None, post_future=None, stream=0):
-        _check(self._lib.tfft_gcconv_grad_exec_input_grad(self._h, gy, post, future, post_future, x, pre, dx, dpre, stream))
+        self._check(self._lib.tfft_gcconv_grad_exec_input_grad(self._h, gy, post, future, post_future, x, pre, dx, dpre, stream))
 
     def tap_grad_ptr(self, x, gy, dh, pre=None, post=None, dskip=None, history=None, pre_history=None, stream=0):
-        _check(self._lib.tfft_gcconv_grad_exec_tap_grad(self._h, x, pre, history, pre_history, gy, post, dh, dskip, stream))
+        self._check(self._lib.tfft_gcconv_grad_exec_tap_grad(self._h, x, pre, history, pre_history, gy, post, dh, dskip, stream))
 
     def input_grad(self, gy, dx, post=None, x=None, pre=None, dpre=None, future=None, post_future=None, stream=None):
         """gy, dx, post, x, pre, dpre, future, post_future: flat CUDA float16 tensors, sequence (b, c) at (b * channels + c) * the
@@ -346,7 +197,7 @@ class TfftGatedChunkedConvGradPlan(_PlanBase):
 
         for t, stride in ((gy, self.gy_seq_stride), (dx, self.dx_seq_stride), (post, self.post_seq_stride), (x, self.x_seq_stride),
                           (pre, self.pre_seq_stride), (dpre, self.dpre_seq_stride)):
-            self._check_seqs(t, stride, self.length)
+            self._check_seqs(t, stride)
         self._check_seqs(future, self.fut_seq_stride, self.future, "futures")
         self._check_seqs(post_future, self.post_fut_seq_stride, self.future, "futures")
         with torch.cuda.device(self.device):
@@ -359,68 +210,34 @@ class TfftGatedChunkedConvGradPlan(_PlanBase):
         import torch
 
         for t, stride in ((x, self.x_seq_stride), (gy, self.gy_seq_stride), (pre, self.pre_seq_stride), (post, self.post_seq_stride)):
-            self._check_seqs(t, stride, self.length)
+            self._check_seqs(t, stride)
         self._check_seqs(history, self.hist_seq_stride, self.history, "histories")
         self._check_seqs(pre_history, self.pre_hist_seq_stride, self.history, "histories")
-        for t, count, what in ((dh, self.channels * self.taps, "tap"), (dskip, self.channels, "skip")):
-            if t is None and what == "skip":
-                continue
-            if not (_is_cuda(t, torch.float32) and t.is_contiguous() and t.device.index == self.device and t.numel() >= count):
-                raise TfftError(5, f"the {what} gradient must be a contiguous CUDA float32 tensor of channels"
-                                   f"{' * taps' if what == 'tap' else ''} elements on the plan's device")
+        self._check_grad(dh, self.channels * self.taps, "tap")
+        if dskip is not None:
+            self._check_grad(dskip, self.channels, "skip")
         with torch.cuda.device(self.device):
             self.tap_grad_ptr(x.data_ptr(), gy.data_ptr(), dh.data_ptr(), _ptr(pre), _ptr(post), _ptr(dskip), _ptr(history), _ptr(pre_history),
                               self._stream(stream))
 
 
-# ---- the convenience functions. They take [B, C, L] VIEWS without copying, under the rules of cconv.py (cconv._strided): a chunk of a
-# longer buffer and its history go to the plan as two pointers and one sequence stride, and so do a gate and its history. The plans of
-# the last GCCONV_CACHE_SIZE (shape, gates, strides, context, device) keys are kept, least recently used first out, one cache per
-# operation; gcconv_cache_clear() releases all three.
+# ---- the convenience functions. They take [B, C, L] VIEWS without copying, under the rules of cconv.py (_conv_common._strided): a
+# chunk of a longer buffer and its history go to the plan as two pointers and one sequence stride, and so do a gate and its history.
+# The plans of the last GCCONV_CACHE_SIZE (shape, gates, strides, context, device) keys are kept, least recently used first out, one
+# cache per operation; gcconv_cache_clear() releases all three.
 GCCONV_CACHE_SIZE = 8
 _fwd_plans = {}
 _dx_plans = {}
 _dh_plans = {}
 
 
-def _cached(cache, key, make):
-    entry = cache.pop(key, None)
-    if entry is None:
-        entry = [make(), None]
-    cache[key] = entry
-    while len(cache) > GCCONV_CACHE_SIZE:
-        cache.pop(next(iter(cache)))[0].close()
-    return entry
-
-
-def _hand_taps(entry, h, skip):
-    """set_taps only when (data_ptr, _version) of h or skip changed since the plan's last call, as gated_long_causal_conv does"""
-    ident = (h.data_ptr(), h._version, None if skip is None else (skip.data_ptr(), skip._version))
-    if not h.is_contiguous() or not (skip is None or skip.is_contiguous()):
-        ident = None                 # a copy's address and version say nothing about its content
-    if ident is None or entry[1] != ident:
-        entry[0].set_taps(h.contiguous().view(-1), None if skip is None else skip.contiguous())
-        entry[1] = ident
-
-
 def gcconv_cache_clear():
     """Destroys the plans the gated_chunked_causal_conv* functions cached."""
-    for cache in (_fwd_plans, _dx_plans, _dh_plans):
-        while cache:
-            cache.popitem()[1][0].close()
+    _binding._cache_clear(_fwd_plans, _dx_plans, _dh_plans)
 
 
-def _check_args(name, seq, others, h, skip):
-    import torch
-
-    ok = _is_cuda(seq, torch.float16) and seq.dim() == 3
-    for t in others:
-        ok = ok and (t is None or (_is_cuda(t, torch.float16) and t.shape == seq.shape and t.device == seq.device))
-    if h is not None:
-        ok = ok and _is_cuda(h, torch.float16) and h.dim() == 2 and h.shape[0] == seq.shape[1] and h.device == seq.device
-    ok = ok and (skip is None or (_is_cuda(skip, torch.float16) and skip.shape == (seq.shape[1],) and skip.device == seq.device))
-    if not ok:
-        raise TfftError(5, f"{name} takes CUDA float16 tensors (B, C, L) for the sequences and gates, h (C, K) and skip (C,) on one device")
+def _takes(name):
+    return f"{name} takes CUDA float16 tensors (B, C, L) for the sequences and gates, h (C, K) and skip (C,) on one device"
 
 
 def _gate_context(ctx, gate_ctx, gate, like, halo, what, gate_what):
@@ -446,24 +263,23 @@ def gated_chunked_causal_conv(x, h, pre=None, post=None, skip=None, history=None
     pre are given. Nothing is copied that the plan can read in place (cconv.py). Returns y [B, C, L], a new tensor."""
     import torch
 
-    _check_args("gated_chunked_causal_conv", x, (pre, post), h, skip)
+    common._check_tap_args(_takes("gated_chunked_causal_conv"), (x,), (pre, post), h, skip)
     rows, channels, length = x.shape
     taps = h.shape[1]
     halo = gcconv_geometry(length, taps, rows, channels)[0]
     x, x_stride = _strided(x)
-    pre, pre_stride = (None, 0) if pre is None else _strided(pre)
-    post, post_stride = (None, 0) if post is None else _strided(post)
+    pre, pre_stride = _strided(pre)
+    post, post_stride = _strided(post)
     hist, phist, hn, hist_stride, phist_stride = _gate_context(history, pre_history, pre, x, halo, "history", "pre_history")
     dev = x.device.index
-    entry = _cached(_fwd_plans, (rows, channels, length, taps, dev, pre is not None, post is not None, x_stride, pre_stride, post_stride, hn,
-                                 hist_stride, phist_stride),
-                    lambda: TfftGatedChunkedConvPlan(rows, channels, length, taps, dev, pre_gate=pre is not None, post_gate=post is not None,
-                                                     in_seq_stride=x_stride, pre_seq_stride=pre_stride, post_seq_stride=post_stride, history=hn,
-                                                     hist_seq_stride=hist_stride, pre_hist_seq_stride=phist_stride))
-    _hand_taps(entry, h, skip)
+    key = (rows, channels, length, taps, dev, pre is not None, post is not None, x_stride, pre_stride, post_stride, hn, hist_stride, phist_stride)
+    entry = _binding._cached(_fwd_plans, GCCONV_CACHE_SIZE, key, lambda: TfftGatedChunkedConvPlan(
+        rows, channels, length, taps, dev, pre_gate=pre is not None, post_gate=post is not None, in_seq_stride=x_stride, pre_seq_stride=pre_stride,
+        post_seq_stride=post_stride, history=hn, hist_seq_stride=hist_stride, pre_hist_seq_stride=phist_stride))
+    common._hand_taps(entry, h, skip)
     y = torch.empty((rows, channels, length), dtype=torch.float16, device=x.device)
-    f = lambda t: None if t is None else _flat(t)      # noqa: E731
-    entry[0].exec(_flat(x), y.view(-1), pre=f(pre), post=f(post), hist=f(hist), pre_hist=f(phist))
+    f = _flat_view
+    entry[0].exec(f(x), y.view(-1), pre=f(pre), post=f(post), hist=f(hist), pre_hist=f(phist))
     return y
 
 
@@ -474,29 +290,27 @@ def gated_chunked_causal_conv_input_grad(gy, h, x=None, pre=None, post=None, ski
     gate or when want_dpre is false."""
     import torch
 
-    _check_args("gated_chunked_causal_conv_input_grad", gy, (x, pre, post), h, skip)
+    common._check_tap_args(_takes("gated_chunked_causal_conv_input_grad"), (gy,), (x, pre, post), h, skip)
     if (pre is None) != (x is None):
         raise TfftError(5, "gated_chunked_causal_conv_input_grad takes x exactly when it takes pre")
     rows, channels, length = gy.shape
     taps = h.shape[1]
     halo = gcconv_geometry(length, taps, rows, channels)[0]
     gy, gy_stride = _strided(gy)
-    post, post_stride = (None, 0) if post is None else _strided(post)
-    x, x_stride = (None, 0) if x is None else _strided(x)
-    pre, pre_stride = (None, 0) if pre is None else _strided(pre)
+    post, post_stride = _strided(post)
+    x, x_stride = _strided(x)
+    pre, pre_stride = _strided(pre)
     fut, pfut, fn, fut_stride, pfut_stride = _gate_context(future, post_future, post, gy, halo, "future", "post_future")
     dev = gy.device.index
-    entry = _cached(_dx_plans, (rows, channels, length, taps, dev, pre is not None, post is not None, gy_stride, post_stride, x_stride, pre_stride,
-                                fn, fut_stride, pfut_stride),
-                    lambda: TfftGatedChunkedConvGradPlan(rows, channels, length, taps, dev, pre_gate=pre is not None, post_gate=post is not None,
-                                                         gy_seq_stride=gy_stride, post_seq_stride=post_stride, x_seq_stride=x_stride,
-                                                         pre_seq_stride=pre_stride, future=fn, fut_seq_stride=fut_stride,
-                                                         post_fut_seq_stride=pfut_stride))
-    _hand_taps(entry, h, skip)
+    key = (rows, channels, length, taps, dev, pre is not None, post is not None, gy_stride, post_stride, x_stride, pre_stride, fn, fut_stride, pfut_stride)
+    entry = _binding._cached(_dx_plans, GCCONV_CACHE_SIZE, key, lambda: TfftGatedChunkedConvGradPlan(
+        rows, channels, length, taps, dev, pre_gate=pre is not None, post_gate=post is not None, gy_seq_stride=gy_stride, post_seq_stride=post_stride,
+        x_seq_stride=x_stride, pre_seq_stride=pre_stride, future=fn, fut_seq_stride=fut_stride, post_fut_seq_stride=pfut_stride))
+    common._hand_taps(entry, h, skip)
     dx = torch.empty((rows, channels, length), dtype=torch.float16, device=gy.device)
     dpre = torch.empty_like(dx) if pre is not None and want_dpre else None
-    f = lambda t: None if t is None else _flat(t)      # noqa: E731
-    entry[0].input_grad(_flat(gy), dx.view(-1), post=f(post), x=f(x), pre=f(pre), dpre=None if dpre is None else dpre.view(-1), future=f(fut),
+    f = _flat_view
+    entry[0].input_grad(f(gy), dx.view(-1), post=f(post), x=f(x), pre=f(pre), dpre=None if dpre is None else dpre.view(-1), future=f(fut),
                         post_future=f(pfut))
     return dx, dpre
 
@@ -506,28 +320,26 @@ def gated_chunked_causal_conv_tap_grad(x, gy, taps, pre=None, post=None, history
     pre * x]; float32 [C, taps], and dskip = dh[:, 0] as a tensor of its own [C]."""
     import torch
 
-    _check_args("gated_chunked_causal_conv_tap_grad", x, (gy, pre, post), None, None)
-    if not _is_cuda(gy, torch.float16):
+    common._check_seq_args(_takes("gated_chunked_causal_conv_tap_grad"), (x,), (gy, pre, post))
+    if gy is None:
         raise TfftError(5, "gated_chunked_causal_conv_tap_grad takes gy, a CUDA float16 tensor of the shape of x")
     rows, channels, length = x.shape
     taps = int(taps)
     halo = gcconv_geometry(length, taps, rows, channels)[0]
     x, x_stride = _strided(x)
     gy, gy_stride = _strided(gy)
-    pre, pre_stride = (None, 0) if pre is None else _strided(pre)
-    post, post_stride = (None, 0) if post is None else _strided(post)
+    pre, pre_stride = _strided(pre)
+    post, post_stride = _strided(post)
     hist, phist, hn, hist_stride, phist_stride = _gate_context(history, pre_history, pre, x, halo, "history", "pre_history")
     dev = x.device.index
-    entry = _cached(_dh_plans, (rows, channels, length, taps, dev, pre is not None, post is not None, x_stride, gy_stride, pre_stride, post_stride,
-                                hn, hist_stride, phist_stride),
-                    lambda: TfftGatedChunkedConvGradPlan(rows, channels, length, taps, dev, pre_gate=pre is not None, post_gate=post is not None,
-                                                         x_seq_stride=x_stride, gy_seq_stride=gy_stride, pre_seq_stride=pre_stride,
-                                                         post_seq_stride=post_stride, history=hn, hist_seq_stride=hist_stride,
-                                                         pre_hist_seq_stride=phist_stride))
+    key = (rows, channels, length, taps, dev, pre is not None, post is not None, x_stride, gy_stride, pre_stride, post_stride, hn, hist_stride, phist_stride)
+    entry = _binding._cached(_dh_plans, GCCONV_CACHE_SIZE, key, lambda: TfftGatedChunkedConvGradPlan(
+        rows, channels, length, taps, dev, pre_gate=pre is not None, post_gate=post is not None, x_seq_stride=x_stride, gy_seq_stride=gy_stride,
+        pre_seq_stride=pre_stride, post_seq_stride=post_stride, history=hn, hist_seq_stride=hist_stride, pre_hist_seq_stride=phist_stride))
     dh = torch.empty((channels, taps), dtype=torch.float32, device=x.device)
     dskip = torch.empty((channels,), dtype=torch.float32, device=x.device)
-    f = lambda t: None if t is None else _flat(t)      # noqa: E731
-    entry[0].tap_grad(_flat(x), _flat(gy), dh, pre=f(pre), post=f(post), dskip=dskip, history=f(hist), pre_history=f(phist))
+    f = _flat_view
+    entry[0].tap_grad(f(x), f(gy), dh, pre=f(pre), post=f(post), dskip=dskip, history=f(hist), pre_history=f(phist))
     return dh, dskip
 
 
