@@ -40,6 +40,9 @@ Thirteen layers, all thin:
   fallback).
 * :mod:`.istftn` — ctypes binding of the short-frame inverse STFT add-on ``include/tfft_istftn.h`` in ``libtfft_istftn.so`` (the
   plans of :mod:`.istft` at the frame lengths 512, 1024 and 2048; layered on ``libtfft_conv.so`` and ``libtfft.so``; no fallback).
+* :mod:`.spec` — ctypes binding of the spectrogram add-on ``include/tfft_spec.h`` in ``libtfft_spec.so`` (power spectrograms and band
+  energies, mel among them, of the frames of :mod:`.stftn` in one kernel; layered on ``libtfft_conv.so`` and ``libtfft.so``; no
+  fallback), the host-side ``Bands`` container and the mel filterbank.
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -79,6 +82,8 @@ from .stftn import (StftNOpts, TfftShortStftPlan, load_stftn_library, short_stft
                     stftn_geometry, stftn_lib_path)
 from .istftn import (IstftNOpts, TfftShortIstftPlan, istftn_cache_clear, istftn_describe, istftn_geometry, istftn_lib_path,  # noqa: F401
                      load_istftn_library, short_istft)
+from .spec import (Bands, SpecOpts, TfftSpectrogramPlan, band_spectrogram, bands_from_dense, load_spec_library, mel_bands,  # noqa: F401
+                   mel_filterbank, power_spectrogram, spec_cache_clear, spec_describe, spec_geometry, spec_lib_path)
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -118,6 +123,8 @@ __all__ = [
     "stftn_lib_path",
     "IstftNOpts", "TfftShortIstftPlan", "istftn_cache_clear", "istftn_describe", "istftn_geometry", "istftn_lib_path",
     "load_istftn_library", "short_istft",
+    "Bands", "SpecOpts", "TfftSpectrogramPlan", "band_spectrogram", "bands_from_dense", "load_spec_library", "mel_bands", "mel_filterbank",
+    "power_spectrogram", "spec_cache_clear", "spec_describe", "spec_geometry", "spec_lib_path",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]

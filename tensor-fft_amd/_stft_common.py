@@ -1,7 +1,7 @@
-"""What the four STFT bindings (stft, istft, stftn, istftn) do the same way: the ctypes prototypes of a library, the owning plan
-wrapper with its tensor checks, the hand-over of a window to a cached plan by identity, and the tensor functions on top. What is
+"""What the STFT bindings (stft, istft, stftn, istftn, and spec on top of them) do the same way: the ctypes prototypes of a library,
+the owning plan wrapper with its tensor checks, the hand-over of a window to a cached plan by identity, and the tensor functions on top. What is
 not about windows and frames (loading, the return-code check, the handle's life cycle, the workspace calls, the cache) is
-_binding.py's. Private: the public names stay in the four modules. No fallback of any kind."""
+_binding.py's. Private: the public names stay in the modules. No fallback of any kind."""
 import ctypes
 
 from . import conv
@@ -23,9 +23,10 @@ def _pitch(n):
     return (_bins(n) + 7) // 8 * 8
 
 
-def _load(path, what, prefix, opts, takes_n, inverse):
+def _load(path, what, prefix, opts, takes_n, inverse, own=None):
     """Loads libtfft.so and libtfft_conv.so, then the add-on at `path` ("the `what` add-on"), and sets the prototypes of its calls
-    <prefix>*: with the frame length in front where the library `takes_n`, with the workspace calls where it is an `inverse`."""
+    <prefix>*: with the frame length in front where the library `takes_n`, with the workspace calls where it is an `inverse`, and
+    with `own`, {name: (restype, argtypes)}, for the calls a library has beyond these or with other arguments."""
     vp, u64, ci, sz = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_size_t
     n = [ctypes.c_uint32] if takes_n else []
     protos = {
@@ -41,6 +42,7 @@ def _load(path, what, prefix, opts, takes_n, inverse):
     }
     if inverse:
         protos.update({"plan_workspace_bytes": (sz, [vp]), "plan_set_workspace": (ci, [vp, vp, sz]), "plan_prepare": (ci, [vp])})
+    protos.update(own or {})
     return _load_addon(conv.load_conv_library, path, what, {prefix + name: proto for name, proto in protos.items()})
 
 

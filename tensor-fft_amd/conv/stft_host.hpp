@@ -1,6 +1,6 @@
-// stft_host.hpp — what the host side of the four STFT libraries (stft, istft, stftn, istftn) does the same way on top of
+// stft_host.hpp — what the host side of the STFT libraries (stft, istft, stftn, istftn, spec) does the same way on top of
 // host_plumbing.hpp: the refusals of a geometry, a shape and a stride, the plan-create sequence, the window, the checks an execution
-// makes before it launches, the grid of the overlap-add and, for the two short-frame libraries, the tables of csrc/k256r.hpp.
+// makes before it launches, the grid of the overlap-add and, for the libraries of the short frame lengths, the tables of csrc/k256r.hpp.
 //
 // The frame length n is a run-time argument everywhere: the 4096 pair passes 4096 and std::to_string(n) spells the messages. A
 // forward plan reads signals and writes frames, an inverse plan reads frames and writes signals; stft_rules says which, and the
@@ -49,8 +49,17 @@ constexpr uint64_t kMaxExtent = uint64_t{1} << 62;       // halves: a byte offse
 
 constexpr uint64_t bins_of(uint64_t n) { return n / 2 + 1; }
 constexpr uint64_t pitch_of(uint64_t n) { return (bins_of(n) + 7) & ~uint64_t{7}; }      // tfft_rplan_spectrum_pitch(n)
-// (count - 1) * stride + len below 2^62 halves, without overflow
-inline bool extent_fits(uint64_t count, uint64_t stride, uint64_t len) { return count == 1 || stride <= (kMaxExtent - len - 1) / (count - 1); }
+// (count - 1) * stride + len below `limit` elements (2^62 halves), without overflow
+inline bool extent_fits(uint64_t count, uint64_t stride, uint64_t len, uint64_t limit = kMaxExtent) {
+  return count == 1 || stride <= (limit - len - 1) / (count - 1);
+}
+
+// The frame side of a plan whose frames are not [RE | IM] planes of n / 2 + 1 halves (the spectrogram plans write fp32): what a
+// frame holds, the default stride, what a stride must be a multiple of (1: anything), and the unit with its size in bytes
+struct frame_layout {
+  uint64_t len, dflt, multiple, elem_bytes;
+  const char* unit;                  // "floats"
+};
 
 // what differs between the four libraries in what they refuse and how they say it
 struct stft_rules {
@@ -89,25 +98,33 @@ inline int check_shape(const stft_rules& rules, uint64_t n, uint64_t rows, uint6
 
 // The strides of the two sides, 0 for the default: `sig_field` / `frame_field` as the options struct names them ("in_sig_stride" /
 // "out_frame_stride", or "out_sig_stride" / "in_frame_stride" with `frames_in`). The input side is looked at first
+// A frame side of another kind comes as `layout`: its extent stays below 2^63 bytes as that of halves does
 inline int check_strides(uint64_t n, uint64_t rows, uint64_t length, uint64_t frames, const char* sig_field, uint64_t sig_stride,
-                         const char* frame_field, uint64_t frame_stride, bool frames_in) {
+                         const char* frame_field, uint64_t frame_stride, bool frames_in, const frame_layout* layout = nullptr) {
   struct side {
     const char* field;
     const char* count;
     uint64_t stride, dflt, blocks, len;
     std::string len_text;
+    uint64_t multiple, limit;
+    std::string limit_text;
   };
-  const side sig = {sig_field, "rows", sig_stride, length, rows, length, "length"};
-  const side frm = {frame_field, "rows * frames", frame_stride, 2 * pitch_of(n), rows * frames, bins_of(n), std::to_string(bins_of(n))};
+  const side sig = {sig_field, "rows", sig_stride, length, rows, length, "length", 8, kMaxExtent, "2^62 halves"};
+  const side frm = layout ? side{frame_field, "rows * frames", frame_stride, layout->dflt, rows * frames, layout->len, std::to_string(layout->len),
+                                 layout->multiple, 2 * kMaxExtent / layout->elem_bytes,
+                                 "2^" + std::to_string(layout->elem_bytes == 4 ? 61 : 62) + " " + layout->unit}
+                          : side{frame_field, "rows * frames", frame_stride, 2 * pitch_of(n), rows * frames, bins_of(n), std::to_string(bins_of(n)), 8,
+                                 kMaxExtent, "2^62 halves"};
   const side* const in_out[2] = {frames_in ? &frm : &sig, frames_in ? &sig : &frm};
   for (const side* s : in_out)
-    if (s->stride && (s->stride % 8 || s->stride < s->len))
-      return fail(TFFT_ERR_ARG, std::string(s->field) + " must be 0 or a multiple of 8 that is >= " + s->len_text);
+    if (s->stride && (s->stride % s->multiple || s->stride < s->len))
+      return fail(TFFT_ERR_ARG, std::string(s->field) + " must be 0 or " +
+                                    (s->multiple > 1 ? "a multiple of " + std::to_string(s->multiple) + " that is >= " : ">= ") + s->len_text);
   for (int i = 0; i < 2; ++i) {
     const side* s = in_out[i];
-    if (!extent_fits(s->blocks, s->stride ? s->stride : s->dflt, s->len))
+    if (!extent_fits(s->blocks, s->stride ? s->stride : s->dflt, s->len, s->limit))
       return fail(TFFT_ERR_ARG, std::string("the ") + (i ? "output" : "input") + " extent (" + s->count + " - 1) * " + s->field + " + " + s->len_text +
-                                    " must be below 2^62 halves");
+                                    " must be below " + s->limit_text);
   }
   return TFFT_OK;
 }
@@ -116,10 +133,13 @@ inline int check_strides(uint64_t n, uint64_t rows, uint64_t length, uint64_t fr
 // num_cus, d_tables, d_window (n halves, the plan's own copy), have_window.
 //
 // The plan-create sequence of all four. `o` holds the defaults on entry; `sig` / `frm` are the signal and the frame stride of Opts.
-// `finish(p, o)` runs on the plan's device: it fills what is the library's own and creates the device state
+// `finish(p, o)` runs on the plan's device: it fills what is the library's own and creates the device state. A library whose
+// frames are no planes of halves passes `frame_side(n, o, layout)`: it refuses what is wrong with the options of its own, after the
+// shape and before the strides, and states the layout of a frame
 template <class Plan, class Opts, class Finish>
 int create_plan(const stft_rules& rules, uint64_t n, uint64_t rows, uint64_t length, uint64_t hop, uint64_t pad, int device_id, const Opts* opts, Opts o,
-                uint64_t Opts::*sig, uint64_t Opts::*frm, Plan** out, void (*destroy)(Plan*), Finish finish) {
+                uint64_t Opts::*sig, uint64_t Opts::*frm, Plan** out, void (*destroy)(Plan*), Finish finish,
+                int (*frame_side)(uint64_t, const Opts&, frame_layout&) = nullptr) {
   g_err.clear();
   if (!out) return fail(TFFT_ERR_ARG, "null plan pointer");
   *out = nullptr;
@@ -127,10 +147,12 @@ int create_plan(const stft_rules& rules, uint64_t n, uint64_t rows, uint64_t len
   int rc = take_opts(opts, (name + "_opts").c_str(), o);
   if (rc) return rc;
   uint64_t frames = 0;
+  frame_layout layout = {};
   rc = check_shape(rules, n, rows, length, hop, pad, o.flags, &frames);
+  if (rc == TFFT_OK && frame_side) rc = frame_side(n, o, layout);
   if (rc == TFFT_OK)
-    rc = rules.inverse ? check_strides(n, rows, length, frames, "out_sig_stride", o.*sig, "in_frame_stride", o.*frm, true)
-                       : check_strides(n, rows, length, frames, "in_sig_stride", o.*sig, "out_frame_stride", o.*frm, false);
+    rc = rules.inverse ? check_strides(n, rows, length, frames, "out_sig_stride", o.*sig, "in_frame_stride", o.*frm, true, frame_side ? &layout : nullptr)
+                       : check_strides(n, rows, length, frames, "in_sig_stride", o.*sig, "out_frame_stride", o.*frm, false, frame_side ? &layout : nullptr);
   if (rc == TFFT_OK) rc = check_launch_iters(o.launch_iters);
   if (rc == TFFT_OK) rc = check_abi(("lib" + name + ".so").c_str());
   if (rc == TFFT_OK) rc = pass_tfft(tfft_device_check(device_id));
@@ -146,7 +168,7 @@ int create_plan(const stft_rules& rules, uint64_t n, uint64_t rows, uint64_t len
   p->pad = pad;
   p->frames = frames;
   p->total = rows * frames;
-  const uint64_t sig_stride = o.*sig ? o.*sig : length, frame_stride = o.*frm ? o.*frm : 2 * pitch_of(n);
+  const uint64_t sig_stride = o.*sig ? o.*sig : length, frame_stride = o.*frm ? o.*frm : frame_side ? layout.dflt : 2 * pitch_of(n);
   p->in_stride = rules.inverse ? frame_stride : sig_stride;
   p->out_stride = rules.inverse ? sig_stride : frame_stride;
   p->launch_iters = o.launch_iters;
