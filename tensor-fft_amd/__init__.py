@@ -43,6 +43,10 @@ Thirteen layers, all thin:
 * :mod:`.spec` — ctypes binding of the spectrogram add-on ``include/tfft_spec.h`` in ``libtfft_spec.so`` (power spectrograms and band
   energies, mel among them, of the frames of :mod:`.stftn` in one kernel; layered on ``libtfft_conv.so`` and ``libtfft.so``; no
   fallback), the host-side ``Bands`` container and the mel filterbank.
+* :mod:`.mistftn` — ctypes binding of the masked short-frame inverse STFT add-on ``include/tfft_mistftn.h`` in ``libtfft_mistftn.so``
+  (the plans of :mod:`.istftn` with a real mask inside the merge, per frame or per bin; layered on ``libtfft_conv.so`` and
+  ``libtfft.so``; no fallback), and :mod:`.stft_autograd`, the ``torch.autograd`` hooks of ``short_stft`` and ``power_spectrogram``
+  whose backward passes are raw-sum masked plans.
 * :mod:`.reference_api` — the reference's own host interface for this path
   (``CreatePlan``, ``PlanWorksOnDevice``, ``GetMaxNoOptInSharedMem``,
   ``DataHandler``, ``DataBatchHandler``, ``ComputeFFT``; reference
@@ -84,6 +88,9 @@ from .istftn import (IstftNOpts, TfftShortIstftPlan, istftn_cache_clear, istftn_
                      load_istftn_library, short_istft)
 from .spec import (Bands, SpecOpts, TfftSpectrogramPlan, band_spectrogram, bands_from_dense, load_spec_library, mel_bands,  # noqa: F401
                    mel_filterbank, power_spectrogram, spec_cache_clear, spec_describe, spec_geometry, spec_lib_path)
+from .mistftn import (MaskedIstftNOpts, TfftMaskedIstftPlan, load_mistftn_library, mask_buffer, masked_istft, mistftn_cache_clear,  # noqa: F401
+                      mistftn_describe, mistftn_geometry, mistftn_lib_path)
+from .stft_autograd import differentiable_power_spectrogram, differentiable_short_stft, stft_autograd_cache_clear  # noqa: F401
 from .reference_api import (  # noqa: F401
     ComputeFFT,
     CreatePlan,
@@ -125,6 +132,9 @@ __all__ = [
     "load_istftn_library", "short_istft",
     "Bands", "SpecOpts", "TfftSpectrogramPlan", "band_spectrogram", "bands_from_dense", "load_spec_library", "mel_bands", "mel_filterbank",
     "power_spectrogram", "spec_cache_clear", "spec_describe", "spec_geometry", "spec_lib_path",
+    "MaskedIstftNOpts", "TfftMaskedIstftPlan", "load_mistftn_library", "mask_buffer", "masked_istft", "mistftn_cache_clear", "mistftn_describe",
+    "mistftn_geometry", "mistftn_lib_path",
+    "differentiable_power_spectrogram", "differentiable_short_stft", "stft_autograd_cache_clear",
     "ComputeFFT", "CreatePlan", "DataBatchHandler", "DataHandler", "GetMaxNoOptInSharedMem",
     "Mode_256", "Mode_4096", "Plan", "PlanWorksOnDevice",
 ]
