@@ -11,7 +11,8 @@
  *     P[g][k] = fp32(gain * fp32(fp32(re)^2 + fp32(im)^2))
  *
  * The squares of binary16 values are exact in fp32, so the sum is rounded once and the product with the gain once more. A power
- * of two such as gain = n^2, which undoes the family's 1 / n scaling, rounds nothing short of overflow. The output is fp32 and
+ * of two such as gain = n^2, which undoes the family's 1 / n scaling, rounds nothing short of overflow; beyond fp32's range the
+ * product is +inf, never a NaN. Not pinned: a product gain * (re^2 + im^2) below 2^-126 (the device may flush it). The output is fp32 and
  * frame-major: frame g at out + g * out_frame_stride floats. The stride defaults to tfft_rplan_spectrum_pitch(n) (264, 520, 1032);
  * otherwise it is a multiple of 4 that is at least n / 2 + 1. Floats behind bin n / 2 of a frame are never written.
  *

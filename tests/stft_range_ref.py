@@ -278,27 +278,30 @@ def _ok(d):
     return _finite(d) and holds(d)
 
 
-def _largest(make, start=0, lo=-40, hi=40):
-    """the largest exponent e in [lo, hi] for which make(e) is finite and meets the contract (the quantities grow with e)"""
+def _largest(make, start=0, lo=-40, hi=40, ok=None):
+    """the largest exponent e in [lo, hi] for which make(e) is finite and meets the contract (the quantities grow with e); `ok` is the
+    test of another module's contract (tests/short_range_ref.py)"""
+    ok = _ok if ok is None else ok
     e = start
-    if _ok(make(e)):
-        while e < hi and _ok(make(e + 1)):
+    if ok(make(e)):
+        while e < hi and ok(make(e + 1)):
             e += 1
     else:
-        while e > lo and not _ok(make(e)):
+        while e > lo and not ok(make(e)):
             e -= 1
-        assert _ok(make(e)), "no exponent meets the contract"
+        assert ok(make(e)), "no exponent meets the contract"
     return e
 
 
-def _largest16(make):
+def _largest16(make, ok=None):
     """the largest positive finite binary16 c for which make(c) meets the contract, by bisection over the bit patterns"""
+    ok = _ok if ok is None else ok
     lo, hi = 1, 0x7BFF
     val = lambda b: np.array(b, np.uint16).view(np.float16)[()]      # noqa: E731
-    assert _ok(make(val(lo))) and not _ok(make(val(hi)))
+    assert ok(make(val(lo))) and not ok(make(val(hi)))
     while hi - lo > 1:
         mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if _ok(make(val(mid))) else (lo, mid)
+        lo, hi = (mid, hi) if ok(make(val(mid))) else (lo, mid)
     return val(lo)
 
 
@@ -353,9 +356,9 @@ def _make_forward(corner, n, seed):
     raise ValueError(corner)
 
 
-def tone(c, k0, length=2 * ir.N):
-    """c cos(2 pi k0 t / 4096) rounded to binary16, [1, length]"""
-    return (float(c) * np.cos(2 * np.pi * ((k0 * np.arange(length)) % ir.N) / ir.N)).astype(np.float16)[None]
+def tone(c, k0, length=2 * ir.N, n=ir.N):
+    """c cos(2 pi k0 t / n) rounded to binary16, [1, length]; n = 4096 unless given"""
+    return (float(c) * np.cos(2 * np.pi * ((k0 * np.arange(length)) % n) / n)).astype(np.float16)[None]
 
 
 def _make_inverse(corner, seed):

@@ -76,11 +76,17 @@ def half_spectra(tf, n, shape):
 
 
 def run_spec(tf, n, shape, gain, band_list=None, extra=0, in_extra=0):
-    """One execution into a NaN-prefilled buffer between guard zones, frame stride = default + extra, signal stride = L + in_extra
-    (NaN halves in the gaps). Returns the [G, per_frame] uint32 bit patterns. Checks on the way: the guards and every float a frame
-    does not hold untouched, one launch of the one kernel."""
+    """run_spec_on for shape `shape` of spec_ref.shapes(n) and its case data"""
     rows, length, hop, pad, iters = sr.shapes(n)[shape]
     x, w, _, _ = half_spectra(tf, n, shape)
+    return run_spec_on(tf, n, x, w, hop, pad, iters, gain, band_list, extra, in_extra)
+
+
+def run_spec_on(tf, n, x, w, hop, pad, iters, gain, band_list=None, extra=0, in_extra=0):
+    """One execution on the signals x [R, L] under the window w into a NaN-prefilled buffer between guard zones, frame stride =
+    default + extra, signal stride = L + in_extra (NaN halves in the gaps). Returns the [G, per_frame] uint32 bit patterns. Checks on
+    the way: the guards and every float a frame does not hold untouched, one launch of the one kernel."""
+    rows, length = x.shape
     nb = len(band_list) if band_list else 0
     per_frame = nb or sn.bins(n)
     stride = (nb or sn.pitch(n)) + extra
